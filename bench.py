@@ -13,8 +13,12 @@ storage/tsdb.go:61 segment model); the group-partial exchange is an RCCL
 reduce over the partials tensor.  value = datapoints all ranks processed
 per second.
 
-CPU baseline: the CPU oracle (restated reference Go path, 'port') timed on
-this box's host cores over a bounded sample of the same workload — a
+A plain run sets up, warms up, times --steps steps, writes the last
+step's partials if --dump-outputs DIR is given, and prints one JSON result
+line.  Everything that takes runs of its own is behind --full:
+
+CPU baseline (--full): the CPU oracle (restated reference Go path, 'port')
+timed on the host cores over a bounded sample of the same workload — a
 reported baseline, not the target.
 """
 import argparse
@@ -49,8 +53,18 @@ def main():
                     default=int(os.environ.get("BYDB_BENCH_SERIES", 10000)))
     ap.add_argument("--dp", type=int,
                     default=int(os.environ.get("BYDB_BENCH_DP", 1_000_000)))
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own "
+                         "beyond the headline figure (today: the CPU-oracle "
+                         "baseline); a plain run only sets up, warms up, "
+                         "times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step returned (the per-group partials) as "
+                         "DIR/<name>.npy float64 arrays")
     ap.add_argument("--skip-cpu-baseline", action="store_true",
-                    default=os.environ.get("BYDB_SKIP_CPU_BASELINE") == "1")
+                    default=os.environ.get("BYDB_SKIP_CPU_BASELINE") == "1",
+                    help="with --full: leave the CPU-oracle baseline out")
     ap.add_argument("--workload", default="i64_sum",
                     choices=["i64_sum", "f64_pred", "group256",
                              "group4096_pred3", "mixed"],
@@ -61,6 +75,8 @@ def main():
                          "configs[5] shape (half int64 + half float64 "
                          "series, two overlapped sessions)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import banyandb_amd as ba
@@ -264,8 +280,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(device) if torch.cuda.is_available() else None
     t_start = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
         lm = sess.last_consume_ms()
         if mixed:
             # overlapped streams: the conservative roofline denominator is
@@ -282,12 +299,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- correctness spot-check (outside the timed region) ----
+    # ---- correctness spot-check (outside the timed region) on what the
+    # last timed step returned: no further GPU work ----
+    parts, parts2 = last if mixed else (last, None)
     if world == 1:
-        parts = sess.finalize_partials()
         total_count = sum(p.count for p in parts)
         if mixed:
-            total_count += sum(p.count for p in sess2.finalize_partials())
+            total_count += sum(p.count for p in parts2)
         if not W["preds"]:
             assert total_count == total_dp_rank, \
                 f"count {total_count} != {total_dp_rank}"
@@ -320,9 +338,19 @@ def main():
         except Exception:
             pass
 
+    if args.dump_outputs and rank == 0:
+        # N > 1: rank 0's own shard partials, as finalize_partials()
+        # handed them to the merge
+        if mixed:
+            dump_partials(args.dump_outputs, parts, W["funcs"], False, "i64_")
+            dump_partials(args.dump_outputs, parts2, W["funcs"], True, "f64_")
+        else:
+            dump_partials(args.dump_outputs, parts, W["funcs"],
+                          W["float"] is True)
+
     cpu_baseline = None
-    if (rank == 0 and world == 1 and not args.skip_cpu_baseline
-            and args.workload == "i64_sum"):
+    if (args.full and rank == 0 and world == 1
+            and not args.skip_cpu_baseline and args.workload == "i64_sum"):
         cpu_baseline = run_cpu_baseline(n_dp)
 
     if rank == 0:
@@ -379,6 +407,35 @@ def main():
     sess.close()
     if mixed:
         sess2.close()
+
+
+def dump_partials(out_dir, parts, funcs, is_float, prefix=""):
+    """--dump-outputs: write the per-group partials the last timed step
+    returned as <out_dir>/<prefix><field>.npy, float64, one entry per
+    group (at most 4096 groups, a few hundred KB in all).  Only the fields
+    the configured aggregate functions define are written: count, the sum
+    (sum_i for int64 sessions, sum_f for float64 ones), min_i / max_i.
+    float64 rounds int64 values past 2^53, so every integer field also
+    gets <field>_lo32.npy with its low 32 bits — the pair is exact."""
+    import numpy as np
+    fields = []
+    if "sum" in funcs:
+        fields.append("sum_f" if is_float else "sum_i")
+    if "count" in funcs:
+        fields.append("count")
+    if "min" in funcs:
+        fields.append("min_i")
+    if "max" in funcs:
+        fields.append("max_i")
+    os.makedirs(out_dir, exist_ok=True)
+    for f in fields:
+        vals = [getattr(p, f) for p in parts]
+        np.save(os.path.join(out_dir, f"{prefix}{f}.npy"),
+                np.array(vals, dtype=np.float64))
+        if f != "sum_f":
+            np.save(os.path.join(out_dir, f"{prefix}{f}_lo32.npy"),
+                    np.array([v & 0xFFFFFFFF for v in vals],
+                             dtype=np.float64))
 
 
 def fast_oracle_part(builder):
