@@ -76,6 +76,43 @@ class Result(C.Structure):
     ]
 
 
+# tag filter operators (modelv1.Condition.BinaryOp values) and tag types
+OP_EQ, OP_NE, OP_LT, OP_GT, OP_LE, OP_GE = 1, 2, 3, 4, 5, 6
+OP_IN, OP_NOT_IN = 9, 10
+TAG_STRING, TAG_INT = 1, 2
+FILTER_MAX_CONDS = 8
+FILTER_MAX_VALUES = 4096
+
+
+class TagCondC(C.Structure):
+    # must mirror bydb_tag_cond in include/bydb_gpu.h exactly
+    _fields_ = [
+        ("slot", C.c_int32),
+        ("op", C.c_int32),
+        ("tag_type", C.c_int32),
+        ("n_values", C.c_uint32),
+        ("values", C.POINTER(C.c_uint8)),
+        ("value_offs", C.POINTER(C.c_uint64)),
+    ]
+
+
+class TagCond:
+    """One tag condition for Session.consume_filter: `op` (OP_*) on the
+    block tag slot 0-2, literal value(s) as stored bytes.  Int literals
+    may be given as Python ints with tag_type=TAG_INT; they are stored as
+    i64_tag_cell bytes.  IN / NOT_IN take a list, every other op one
+    value."""
+
+    def __init__(self, slot, op, values, tag_type=TAG_STRING):
+        if isinstance(values, (bytes, int)):
+            values = [values]
+        self.slot = slot
+        self.op = op
+        self.tag_type = tag_type
+        self.values = [i64_tag_cell(v) if isinstance(v, int) else bytes(v)
+                       for v in values]
+
+
 def _build_if_possible():
     from banyandb_amd.build import build
     return build(verbose=False)
@@ -137,6 +174,9 @@ def _load():
     lib.bydb_consume_multi.argtypes = [C.c_void_p, C.c_int64, C.c_int64,
                                        C.POINTER(u8p), C.POINTER(C.c_uint64),
                                        C.c_int]
+    lib.bydb_consume_filter.restype = C.c_int
+    lib.bydb_consume_filter.argtypes = [C.c_void_p, C.c_int64, C.c_int64,
+                                        C.POINTER(TagCondC), C.c_int]
     lib.bydb_finalize.restype = C.c_int
     lib.bydb_finalize.argtypes = [C.c_void_p, C.POINTER(Result), C.c_int64]
     lib.bydb_finalize_partials.restype = C.c_int
@@ -474,6 +514,28 @@ class Session:
             return
         buf = (C.c_uint8 * max(len(pred), 1)).from_buffer_copy(pred or b"\0")
         self._ck(_lib.bydb_consume(self._h, min_ts, max_ts, buf, len(pred)))
+
+    def consume_filter(self, conds, min_ts=INT64_MIN, max_ts=INT64_MAX):
+        """Scan under ANDed TagCond conditions (EQ, NE, LT, LE, GT, GE, IN,
+        NOT_IN); an empty list is an unfiltered scan."""
+        arr = (TagCondC * max(len(conds), 1))()
+        keep = []
+        for i, c in enumerate(conds):
+            blob = b"".join(c.values)
+            offs = [0]
+            for v in c.values:
+                offs.append(offs[-1] + len(v))
+            buf = (C.c_uint8 * max(len(blob), 1)).from_buffer_copy(blob or b"\0")
+            oa = (C.c_uint64 * len(offs))(*offs)
+            keep.append((buf, oa))
+            arr[i].slot = c.slot
+            arr[i].op = c.op
+            arr[i].tag_type = c.tag_type
+            arr[i].n_values = len(c.values)
+            arr[i].values = C.cast(buf, C.POINTER(C.c_uint8))
+            arr[i].value_offs = oa
+        self._ck(_lib.bydb_consume_filter(self._h, min_ts, max_ts, arr,
+                                          len(conds)))
 
     def finalize(self):
         out = (Result * self.n_groups)()

@@ -1252,6 +1252,291 @@ __global__ __launch_bounds__(WAVE) void k_resolve_plain(
     }
 }
 
+// ---------------- tag filter operators ----------------
+// The reference evaluates a measure query's tag conditions per row through
+// the TagFilter tree parseFilter builds (pkg/query/logical/
+// tag_filter.go:144-193).  The scan above never sees tag values — it
+// consumes PredBlocks and the combined flag byte — so the eight scalar
+// operators only need their own resolve stage: the same two prepasses as
+// the equality path, evaluating every condition of a slot against each
+// dictionary value (or plain row) and ANDing the results into the slot's
+// code mask (or match bitmap).  Match rules (header comment of
+// include/bydb_gpu.h restates them with the full citations):
+//   EQ  bytes equal, nil never (eqTag.Match :426-432)
+//   NE / NOT_IN  notTag over EQ / IN — TRUE on nil (:168, :189, :370-376)
+//   IN  BelongTo, nil never (:405-411; expr_literal.go:84-92, 260-268)
+//   GT/GE/LT/LE  c = literal.Compare(value): c<0 / c<=0 / c>0 / c>=0, nil
+//       never (rangeTag.Match :465-503); string c = strings.Compare, int
+//       c = int(lit - val) with wrapping int64 subtraction
+//       (expr_literal.go:65-70, 241-246)
+// Conditions are ANDed (andLogicalNode); OR across conditions is out of
+// scope.
+struct FilterCond {
+    GroupDomain set;        // IN / NOT_IN: open-addressing value set
+    const uint8_t *lit;     // every other op: the single literal
+    uint64_t lit_len;
+    int64_t lit_i;          // decoded int literal (int-typed ranges)
+    uint8_t op;             // BYDB_OP_*
+    uint8_t is_int;         // BYDB_TAG_INT
+    uint8_t _p[6];
+};
+
+// conditions sorted by slot: slot sl owns c[first[sl] .. first[sl+1])
+struct FilterSet {
+    FilterCond c[BYDB_FILTER_MAX_CONDS];
+    int first[4];
+    uint8_t all_neg[3];     // every condition of the slot is NE / NOT_IN
+    uint8_t _p;
+    int n_slots;            // highest conditioned slot + 1
+};
+
+// strings.Compare(a, b) on raw bytes: a proper prefix sorts first
+__device__ __forceinline__ int bytes_compare(const uint8_t *a, uint64_t alen,
+                                             const uint8_t *b, uint64_t blen) {
+    uint64_t n = alen < blen ? alen : blen;
+    for (uint64_t k = 0; k < n; k++)
+        if (a[k] != b[k]) return a[k] < b[k] ? -1 : 1;
+    return alen < blen ? -1 : alen > blen ? 1 : 0;
+}
+
+// convert.BytesToInt64 (number.go:33-46): BE cell with the sign bit flipped
+__device__ __forceinline__ int64_t i64_from_cell(const uint8_t *p) {
+    uint64_t u = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) u = (u << 8) | p[i];
+    return (int64_t)(u ^ (1ull << 63));
+}
+
+// All of one slot's conditions against one tag value (nil: v unused).
+__device__ bool filter_match(const FilterSet &fs, int slot, const uint8_t *v,
+                             uint64_t len, bool nil) {
+    for (int i = fs.first[slot]; i < fs.first[slot + 1]; i++) {
+        const FilterCond &c = fs.c[i];
+        bool m;
+        if (c.op == BYDB_OP_EQ || c.op == BYDB_OP_NE) {
+            bool eq = !nil && len == c.lit_len &&
+                      bytes_compare(c.lit, c.lit_len, v, len) == 0;
+            m = c.op == BYDB_OP_EQ ? eq : !eq;
+        } else if (c.op == BYDB_OP_IN || c.op == BYDB_OP_NOT_IN) {
+            bool in = !nil && domain_lookup(&c.set, v, len) != GID_NONE;
+            m = c.op == BYDB_OP_IN ? in : !in;
+        } else if (nil) {
+            m = false;      // Compare returns ok=false
+        } else {
+            int cmp;        // sign of literal.Compare(value)
+            if (c.is_int) {
+                if (len != 8) return false;
+                // Go int64 subtraction wraps: take the sign of the
+                // two's-complement difference, not of the true one
+                int64_t d = (int64_t)((uint64_t)c.lit_i -
+                                      (uint64_t)i64_from_cell(v));
+                cmp = d < 0 ? -1 : d > 0 ? 1 : 0;
+            } else {
+                cmp = bytes_compare(c.lit, c.lit_len, v, len);
+            }
+            m = c.op == BYDB_OP_GT   ? cmp < 0
+                : c.op == BYDB_OP_GE ? cmp <= 0
+                : c.op == BYDB_OP_LT ? cmp > 0
+                                     : cmp >= 0;
+        }
+        if (!m) return false;
+    }
+    return true;
+}
+
+// Resolve one conditioned slot of one block (dictionary columns): parse
+// the dictionary header once, evaluate all of the slot's conditions per
+// dictionary value into the code mask.  Verdicts beyond the equality
+// path's uniform CLEAR / SKIP: a mask covering every code the dictionary
+// defines is CLEAR and an empty mask is SKIP even when the block has many
+// runs (NE of an absent value, or a wide range, must not push row-varying
+// blocks onto the walker path); a block without the column is all-nil —
+// CLEAR when every condition of the slot is negated, else SKIP.  A CLEAR
+// slot is marked `disabled` for this block, so a walk forced by another
+// slot treats it as no constraint.
+__device__ int resolve_one_filter(const uint8_t *__restrict__ payload,
+                                  const uint8_t *__restrict__ sidecar,
+                                  const bydb_block_desc *__restrict__ bd,
+                                  int slot, const FilterSet &fs,
+                                  PredBlock *out) {
+    uint64_t toff = slot == 0 ? bd->tag_off : slot == 1 ? bd->tag2_off : bd->tag3_off;
+    uint64_t tlen = slot == 0 ? bd->tag_len : slot == 1 ? bd->tag2_len : bd->tag3_len;
+    PredBlock pb;
+    for (int i = 0; i < 4; i++) pb.mask[i] = 0;
+    pb.rle_bit_off = 0; pb.nentries = 0; pb.width = 0;
+    pb.active = 0; pb.err = 0; pb.uniform = 0; pb.plain = 0;
+    pb.disabled = 0;
+    if (fs.first[slot] == fs.first[slot + 1]) {   // no condition on the slot
+        pb.disabled = 1;
+        *out = pb;
+        return PF_CLEAR;
+    }
+    if (tlen == 0) {                              // all-nil block
+        if (fs.all_neg[slot]) { pb.disabled = 1; *out = pb; return PF_CLEAR; }
+        *out = pb;
+        return PF_SKIP;
+    }
+    const bool in_sidecar = (toff & TAG_SIDECAR_BIT) != 0;
+    const uint8_t *base = in_sidecar ? sidecar : payload;
+    const uint8_t *p = base + (toff & ~TAG_SIDECAR_BIT);
+    const uint8_t *end = p + tlen;
+    if (*p == BYDB_ENC_PLAIN) {
+        // host-normalized plain column: k_resolve_plain_filter fills the
+        // match bitmap (an unnormalized plain stream is a loud error)
+        if (!in_sidecar) { pb.err = 1; *out = pb; return PF_ERR; }
+        pb.active = 1;
+        pb.plain = 1;
+        *out = pb;
+        return PF_WALK;
+    }
+    if (*p != BYDB_ENC_DICTIONARY) { pb.err = 1; *out = pb; return PF_ERR; }
+    p++;
+    pb.active = 1;
+    uint64_t count = 0;
+    unsigned sh = 0;
+    while (p < end) {
+        uint8_t c = *p++;
+        count |= (uint64_t)(c & 0x7f) << sh;
+        if (c < 0x80) break;
+        sh += 7;
+    }
+    uint64_t ll = 0;
+    const uint8_t *lens_blk = dict_section(p, end, &ll);
+    if (!lens_blk) { pb.err = 1; *out = pb; return PF_ERR; }
+    p = lens_blk + ll;
+    uint64_t vl = 0;
+    const uint8_t *vals = dict_section(p, end, &vl);
+    if (!vals) { pb.err = 1; *out = pb; return PF_ERR; }
+    p = vals + vl;
+    uint8_t wt = lens_blk[0];
+    uint32_t wbytes = wt == 0 ? 1 : wt == 1 ? 2 : wt == 2 ? 4 : 8;
+    const uint8_t *lp = lens_blk + 1;
+    uint64_t voff = 0;
+    bool any = false, all = true;
+    for (uint64_t v = 0; v < count && v < 256; v++) {
+        uint64_t alen = 0;
+        for (uint32_t b = 0; b < wbytes; b++) alen = (alen << 8) | lp[v * wbytes + b];
+        uint64_t vlen = alen ? alen - 1 : 0;
+        if (filter_match(fs, slot, vals + voff, vlen, alen == 0)) {
+            pb.mask[(v >> 6) & 3] |= 1ull << (v & 63);
+            any = true;
+        } else {
+            all = false;
+        }
+        voff += vlen;
+    }
+    uint64_t bit0 = ((uint64_t)(p - base)) * 8;
+    uint32_t nentries = (uint32_t)rd_bits_be(base, bit0, 32);
+    uint32_t width = nentries ? (uint32_t)rd_bits_be(base, bit0 + 32, 8) : 0;
+    pb.nentries = nentries;
+    pb.width = (uint8_t)width;
+    pb.rle_bit_off = (bit0 + 40) | (in_sidecar ? TAG_SIDECAR_BIT : 0);
+    int verdict = PF_WALK;
+    if (!any) {
+        verdict = PF_SKIP;
+    } else if (all && count <= 256) {
+        pb.disabled = 1;
+        verdict = PF_CLEAR;
+    } else if (nentries == 2) {
+        uint64_t code = rd_bits_be(base, bit0 + 40, width);
+        uint64_t cnt = rd_bits_be(base, bit0 + 40 + width, width);
+        if (cnt >= bd->count) {
+            pb.uniform = 1;
+            bool match = (pb.mask[(code >> 6) & 3] >> (code & 63)) & 1;
+            verdict = match ? PF_CLEAR : PF_SKIP;
+        }
+    }
+    *out = pb;
+    return verdict;
+}
+
+// One fused launch over blocks, the shape of k_resolve_preds: every
+// conditioned slot of a block resolves against one read of its descriptor,
+// and the combined flag byte + walk-block census come out the same way.
+__global__ void k_resolve_filter(
+    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
+    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
+    FilterSet fs, PredBlock *__restrict__ out, uint8_t *__restrict__ flags,
+    uint32_t *__restrict__ walk_count) {
+    int64_t bi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint8_t f = PF_CLEAR;
+    if (bi < n_blocks) {
+        const bydb_block_desc *bd = &blocks[bi];
+        for (int sl = 0; sl < fs.n_slots; sl++) {
+            PredBlock pb;
+            int v = resolve_one_filter(payload, sidecar, bd, sl, fs, &pb);
+            out[(int64_t)sl * n_blocks + bi] = pb;
+            if (v == PF_ERR) { f = PF_ERR; break; }
+            if (v == PF_SKIP) { f = PF_SKIP; break; }
+            if (v == PF_WALK) f = PF_WALK;
+        }
+        flags[bi] = f;
+    }
+    uint64_t wmask = __ballot(bi < n_blocks && f == PF_WALK);
+    if ((threadIdx.x & 63) == 0 && wmask)
+        atomicAdd(walk_count, (uint32_t)__popcll(wmask));
+}
+
+// Plain-column stage, the shape of k_resolve_plain: one wave per block, a
+// wave prefix scan over the value lengths for the payload offsets, all of
+// the slot's conditions per row (nil rows — stored length 0 — follow the
+// nil rules), one ballot word per 64 rows into the bitmap arena.
+__global__ __launch_bounds__(WAVE) void k_resolve_plain_filter(
+    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
+    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
+    FilterSet fs, int slot, PredBlock *__restrict__ out,
+    uint64_t *__restrict__ bm, uint32_t *__restrict__ ctr,
+    uint64_t bm_cap_streams) {
+    const int lane = threadIdx.x;
+    for (int64_t bi = blockIdx.x; bi < n_blocks; bi += gridDim.x) {
+        PredBlock pb = out[bi];
+        if (!pb.plain || pb.err) continue;
+        const bydb_block_desc *bd = &blocks[bi];
+        uint64_t toff = slot == 0 ? bd->tag_off
+                                  : slot == 1 ? bd->tag2_off : bd->tag3_off;
+        const uint8_t *p = (toff & TAG_SIDECAR_BIT)
+                               ? sidecar + (toff & ~TAG_SIDECAR_BIT)
+                               : payload + toff;
+        p++;  // ENC_PLAIN
+        uint64_t n = (uint64_t)p[0] | ((uint64_t)p[1] << 8) |
+                     ((uint64_t)p[2] << 16) | ((uint64_t)p[3] << 24);
+        p += 4;
+        uint8_t wt = *p++;
+        uint32_t wbytes = wt == 0 ? 1 : wt == 1 ? 2 : wt == 2 ? 4 : 8;
+        const uint8_t *lens = p;
+        const uint8_t *vals = lens + n * wbytes;
+        if (n != (uint64_t)bd->count || n > (uint64_t)PLAIN_BM_WORDS * 64) {
+            if (lane == 0) out[bi].err = 1;
+            continue;
+        }
+        uint32_t slot_id = 0;
+        if (lane == 0) slot_id = atomicAdd(ctr, 1u);
+        slot_id = (uint32_t)__shfl((int)slot_id, 0);
+        if (slot_id >= bm_cap_streams) {
+            if (lane == 0) out[bi].err = 1;   // arena exhausted: loud
+            continue;
+        }
+        uint64_t w0 = (uint64_t)slot_id * PLAIN_BM_WORDS;
+        uint64_t carry = 0;  // payload bytes consumed by prior chunks
+        for (uint64_t base = 0; base < n; base += WAVE) {
+            uint64_t row = base + (uint64_t)lane;
+            uint64_t lp1 = 0;
+            if (row < n)
+                for (uint32_t b = 0; b < wbytes; b++)
+                    lp1 = (lp1 << 8) | lens[row * wbytes + b];
+            uint64_t vlen = lp1 ? lp1 - 1 : 0;
+            uint64_t incl = wave_incl_scan(vlen, lane);
+            uint64_t myoff = carry + incl - vlen;
+            bool match = row < n &&
+                         filter_match(fs, slot, vals + myoff, vlen, lp1 == 0);
+            uint64_t word = __ballot(match);
+            if (lane == 0) bm[w0 + (base >> 6)] = word;
+            carry += readlane64(incl, WAVE - 1);
+        }
+        if (lane == 0) out[bi].rle_bit_off = w0;
+    }
+}
+
 // Fold arithmetic-progression blocks (Const dd=0 / DeltaConst) under a
 // per-row predicate: walk rows 64 at a time through the RLE runs.
 __device__ void fold_arith_pred(int64_t first, int64_t dd, int64_t r0,
@@ -3087,6 +3372,11 @@ struct bydb_session {
     uint32_t dom_n[3] = {};
     uint8_t *d_pred_bytes = nullptr;
     uint64_t pred_bytes_cap = 0;
+    // tag filter operators: literals + IN-set tables of the last
+    // bydb_consume_filter, and the host staging copy they upload from
+    uint8_t *d_filter = nullptr;
+    uint64_t filter_cap = 0;
+    std::vector<uint8_t> filter_stage;
     // plain (non-dictionary) tag columns: host-normalized sidecar arena +
     // per-row match bitmaps filled by k_resolve_plain
     uint8_t *d_sidecar = nullptr;
@@ -3150,6 +3440,7 @@ extern "C" void bydb_session_destroy(bydb_session *s) {
     if (s->d_partials) (void)hipFree(s->d_partials);
     if (s->d_preds) (void)hipFree(s->d_preds);
     if (s->d_pred_bytes) (void)hipFree(s->d_pred_bytes);
+    if (s->d_filter) (void)hipFree(s->d_filter);
     if (s->d_segs) (void)hipFree(s->d_segs);
     if (s->d_groups) (void)hipFree(s->d_groups);
     if (s->d_gmap) (void)hipFree(s->d_gmap);
@@ -3474,6 +3765,29 @@ extern "C" int bydb_reset(bydb_session *s) {
     return BYDB_OK;
 }
 
+static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
+                       PredBlock *preds, int n_preds);
+
+// PredBlock / flag-byte / walk-census buffers for the resolve prepasses
+static int ensure_pred_buffers(bydb_session *s) {
+    if (s->preds_cap < s->n_blocks * 3) {
+        if (s->d_preds) (void)hipFree(s->d_preds);
+        HIP_TRY(s, hipMalloc(&s->d_preds,
+                             sizeof(PredBlock) * (size_t)s->n_blocks * 3));
+        s->preds_cap = s->n_blocks * 3;
+    }
+    if (s->pred_flags_cap < s->n_blocks) {
+        if (s->d_pred_flags) (void)hipFree(s->d_pred_flags);
+        HIP_TRY(s, hipMalloc(&s->d_pred_flags, (size_t)s->n_blocks));
+        s->pred_flags_cap = s->n_blocks;
+    }
+    if (!s->d_walk_count)
+        HIP_TRY(s, hipMalloc(&s->d_walk_count, sizeof(uint32_t)));
+    HIP_TRY(s, hipMemsetAsync(s->d_walk_count, 0, sizeof(uint32_t),
+                              s->stream));
+    return BYDB_OK;
+}
+
 extern "C" int bydb_consume_multi(bydb_session *s, int64_t min_ts,
                                   int64_t max_ts, const uint8_t *const *preds_in,
                                   const uint64_t *pred_lens, int n_preds) {
@@ -3486,21 +3800,8 @@ extern "C" int bydb_consume_multi(bydb_session *s, int64_t min_ts,
     while (n_preds > 0 && pred_lens[n_preds - 1] == 0) n_preds--;
     PredBlock *preds = nullptr;
     if (n_preds > 0) {
-        if (s->preds_cap < s->n_blocks * 3) {
-            if (s->d_preds) (void)hipFree(s->d_preds);
-            HIP_TRY(s, hipMalloc(&s->d_preds,
-                                 sizeof(PredBlock) * (size_t)s->n_blocks * 3));
-            s->preds_cap = s->n_blocks * 3;
-        }
-        if (s->pred_flags_cap < s->n_blocks) {
-            if (s->d_pred_flags) (void)hipFree(s->d_pred_flags);
-            HIP_TRY(s, hipMalloc(&s->d_pred_flags, (size_t)s->n_blocks));
-            s->pred_flags_cap = s->n_blocks;
-        }
-        if (!s->d_walk_count)
-            HIP_TRY(s, hipMalloc(&s->d_walk_count, sizeof(uint32_t)));
-        HIP_TRY(s, hipMemsetAsync(s->d_walk_count, 0, sizeof(uint32_t),
-                                  s->stream));
+        int prc = ensure_pred_buffers(s);
+        if (prc != BYDB_OK) return prc;
         uint64_t total = 0;
         for (int i = 0; i < n_preds; i++) total += pred_lens[i];
         if (s->pred_bytes_cap < total) {
@@ -3557,6 +3858,13 @@ extern "C" int bydb_consume_multi(bydb_session *s, int64_t min_ts,
         }
         preds = s->d_preds;
     }
+    return launch_scan(s, min_ts, max_ts, preds, n_preds);
+}
+
+// The scan launch shared by every consume entry point: segment index and
+// group resolve (once per part), kernel selection, light + heavy pass.
+static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
+                       PredBlock *preds, int n_preds) {
     int flags = 0;
     if (s->func_mask & ((1u << BYDB_AGG_MIN) | (1u << BYDB_AGG_MAX)))
         flags |= KF_NEED_VALUES;
@@ -3741,6 +4049,201 @@ extern "C" int bydb_consume(bydb_session *s, int64_t min_ts, int64_t max_ts,
     const uint8_t *preds[1] = {pred};
     uint64_t lens[1] = {pred_len};
     return bydb_consume_multi(s, min_ts, max_ts, preds, lens, 1);
+}
+
+// Scan under ANDed tag conditions (header: "tag filter operators").  The
+// host validates, sorts the conditions by slot, and uploads one arena —
+// u64 section (set value offsets, set hashes), u32 section (set slots),
+// byte section (literals and set values) — in a single copy.  IN / NOT_IN
+// lists become the open-addressing table the group-by domain uses, so the
+// device probes once per value instead of comparing n_values times.  The
+// two filter resolves then feed the unchanged scan launch.
+extern "C" int bydb_consume_filter(bydb_session *s, int64_t min_ts,
+                                   int64_t max_ts, const bydb_tag_cond *conds,
+                                   int n_conds) {
+    HIP_TRY(s, hipSetDevice(s->device));
+    if (!s->d_acc) { s->err = "configure first"; return BYDB_ERR_STATE; }
+    if (s->n_blocks == 0) { s->err = "no part resident"; return BYDB_ERR_STATE; }
+    if (n_conds < 0 || n_conds > BYDB_FILTER_MAX_CONDS ||
+        (n_conds > 0 && conds == nullptr)) {
+        s->err = "n_conds must be 0..8";
+        return BYDB_ERR_BAD_ARG;
+    }
+    uint64_t total_values = 0;
+    for (int i = 0; i < n_conds; i++) {
+        const bydb_tag_cond *c = &conds[i];
+        const bool is_set = c->op == BYDB_OP_IN || c->op == BYDB_OP_NOT_IN;
+        const bool is_range = c->op == BYDB_OP_LT || c->op == BYDB_OP_GT ||
+                              c->op == BYDB_OP_LE || c->op == BYDB_OP_GE;
+        if (c->slot < 0 || c->slot > 2) {
+            s->err = "filter condition slot must be 0..2";
+            return BYDB_ERR_BAD_ARG;
+        }
+        if (!is_set && !is_range && c->op != BYDB_OP_EQ &&
+            c->op != BYDB_OP_NE) {
+            s->err = "unknown filter operator";
+            return BYDB_ERR_BAD_ARG;
+        }
+        if (c->tag_type != BYDB_TAG_STRING && c->tag_type != BYDB_TAG_INT) {
+            s->err = "unknown filter tag type";
+            return BYDB_ERR_BAD_ARG;
+        }
+        if (is_set ? c->n_values < 1 : c->n_values != 1) {
+            s->err = is_set ? "IN / NOT_IN need at least one value"
+                            : "operator takes exactly one value";
+            return BYDB_ERR_BAD_ARG;
+        }
+        total_values += c->n_values;
+        if (total_values > BYDB_FILTER_MAX_VALUES) {
+            s->err = "more than 4096 filter values in one call";
+            return BYDB_ERR_BAD_ARG;
+        }
+        if (c->value_offs == nullptr ||
+            (c->values == nullptr &&
+             c->value_offs[c->n_values] != c->value_offs[0])) {
+            s->err = "filter condition values missing";
+            return BYDB_ERR_BAD_ARG;
+        }
+        for (uint32_t v = 0; v < c->n_values; v++)
+            if (c->value_offs[v + 1] < c->value_offs[v]) {
+                s->err = "filter value offsets must ascend";
+                return BYDB_ERR_BAD_ARG;
+            }
+        if (is_range && c->tag_type == BYDB_TAG_INT &&
+            c->value_offs[1] - c->value_offs[0] != 8) {
+            s->err = "int range literal must be an 8-byte cell";
+            return BYDB_ERR_BAD_ARG;
+        }
+    }
+    if (n_conds == 0) return launch_scan(s, min_ts, max_ts, nullptr, 0);
+
+    // conditions sorted by slot (stable), arena sections built on the host
+    int order[BYDB_FILTER_MAX_CONDS];
+    int n_ord = 0;
+    FilterSet fs;
+    memset(&fs, 0, sizeof(fs));
+    for (int sl = 0; sl < 3; sl++) {
+        fs.first[sl] = n_ord;
+        fs.all_neg[sl] = 1;
+        for (int i = 0; i < n_conds; i++)
+            if (conds[i].slot == sl) {
+                order[n_ord++] = i;
+                if (conds[i].op != BYDB_OP_NE && conds[i].op != BYDB_OP_NOT_IN)
+                    fs.all_neg[sl] = 0;
+                fs.n_slots = sl + 1;
+            }
+    }
+    fs.first[3] = n_ord;
+    std::vector<uint64_t> a64;
+    std::vector<uint32_t> a32;
+    std::vector<uint8_t> a8;
+    struct SetPos { uint64_t hashes, offs, gids; uint32_t tsize; };
+    SetPos pos[BYDB_FILTER_MAX_CONDS];
+    uint64_t lit_pos[BYDB_FILTER_MAX_CONDS];
+    for (int k = 0; k < n_ord; k++) {
+        const bydb_tag_cond *c = &conds[order[k]];
+        const uint64_t v0 = c->value_offs[0];
+        const uint64_t blob_len = c->value_offs[c->n_values] - v0;
+        lit_pos[k] = a8.size();
+        if (blob_len)
+            a8.insert(a8.end(), c->values + v0, c->values + v0 + blob_len);
+        pos[k].tsize = 0;
+        if (c->op != BYDB_OP_IN && c->op != BYDB_OP_NOT_IN) continue;
+        uint32_t tsize = 4;
+        while (tsize < c->n_values * 4) tsize <<= 1;
+        pos[k].tsize = tsize;
+        pos[k].offs = a64.size();
+        for (uint32_t v = 0; v <= c->n_values; v++)
+            a64.push_back(lit_pos[k] + (c->value_offs[v] - v0));
+        pos[k].hashes = a64.size();
+        a64.resize(a64.size() + tsize, 0);
+        pos[k].gids = a32.size();
+        a32.resize(a32.size() + tsize, GID_NONE);
+        for (uint32_t v = 0; v < c->n_values; v++) {
+            uint64_t h = fnv1a(c->values + c->value_offs[v],
+                               c->value_offs[v + 1] - c->value_offs[v]);
+            uint32_t sl = (uint32_t)h & (tsize - 1);
+            while (a32[pos[k].gids + sl] != GID_NONE) sl = (sl + 1) & (tsize - 1);
+            a64[pos[k].hashes + sl] = h;
+            a32[pos[k].gids + sl] = v;
+        }
+    }
+    const uint64_t off32 = a64.size() * sizeof(uint64_t);
+    const uint64_t off8 = off32 + a32.size() * sizeof(uint32_t);
+    const uint64_t arena_len = off8 + a8.size();
+    s->filter_stage.resize(arena_len ? arena_len : 1);
+    if (!a64.empty()) memcpy(s->filter_stage.data(), a64.data(), off32);
+    if (!a32.empty())
+        memcpy(s->filter_stage.data() + off32, a32.data(), off8 - off32);
+    if (!a8.empty()) memcpy(s->filter_stage.data() + off8, a8.data(), a8.size());
+    if (s->filter_cap < s->filter_stage.size()) {
+        if (s->d_filter) { (void)hipFree(s->d_filter); s->d_filter = nullptr; }
+        uint64_t ncap = 4096;
+        while (ncap < s->filter_stage.size()) ncap *= 2;
+        HIP_TRY(s, hipMalloc(&s->d_filter, ncap));
+        s->filter_cap = ncap;
+    }
+    HIP_TRY(s, hipMemcpyAsync(s->d_filter, s->filter_stage.data(),
+                              s->filter_stage.size(), hipMemcpyHostToDevice,
+                              s->stream));
+    const uint64_t *d64 = (const uint64_t *)s->d_filter;
+    const uint32_t *d32 = (const uint32_t *)(s->d_filter + off32);
+    const uint8_t *d8 = s->d_filter + off8;
+    for (int k = 0; k < n_ord; k++) {
+        const bydb_tag_cond *c = &conds[order[k]];
+        FilterCond *fc = &fs.c[k];
+        fc->op = (uint8_t)c->op;
+        fc->is_int = c->tag_type == BYDB_TAG_INT;
+        if (pos[k].tsize) {
+            fc->set.blob = d8;
+            fc->set.offs = d64 + pos[k].offs;
+            fc->set.hashes = d64 + pos[k].hashes;
+            fc->set.gids = d32 + pos[k].gids;
+            fc->set.table_size = pos[k].tsize;
+            fc->set.n = c->n_values;
+        } else {
+            fc->lit = d8 + lit_pos[k];
+            fc->lit_len = c->value_offs[1] - c->value_offs[0];
+            if (fc->is_int && fc->lit_len == 8) {
+                uint64_t u = 0;
+                for (int b = 0; b < 8; b++)
+                    u = (u << 8) | c->values[c->value_offs[0] + b];
+                fc->lit_i = (int64_t)(u ^ (1ull << 63));
+            }
+        }
+    }
+    int rc = ensure_pred_buffers(s);
+    if (rc != BYDB_OK) return rc;
+    const int rthreads = 256;
+    const int rblocks = (int)((s->n_blocks + rthreads - 1) / rthreads);
+    hipLaunchKernelGGL(k_resolve_filter, dim3(rblocks), dim3(rthreads), 0,
+                       s->stream, s->d_payload, s->d_sidecar, s->d_blocks,
+                       s->n_blocks, fs, s->d_preds, s->d_pred_flags,
+                       s->d_walk_count);
+    HIP_TRY(s, hipGetLastError());
+    // plain columns: one bitmap per normalized (block,slot) stream at most,
+    // counted at part_append — the arena is sized without a round-trip
+    if (s->n_plain_host > 0) {
+        uint64_t words = s->n_plain_host * PLAIN_BM_WORDS;
+        if (words > s->pred_bm_cap) {
+            if (s->d_pred_bm) (void)hipFree(s->d_pred_bm);
+            HIP_TRY(s, hipMalloc(&s->d_pred_bm, words * sizeof(uint64_t)));
+            s->pred_bm_cap = words;
+        }
+        HIP_TRY(s, hipMemsetAsync(s->d_plain_ctr, 0, sizeof(uint32_t),
+                                  s->stream));
+        int pgrid = (int)(s->n_blocks < 65535 ? s->n_blocks : 65535);
+        for (int sl = 0; sl < fs.n_slots; sl++) {
+            if (fs.first[sl] == fs.first[sl + 1]) continue;
+            hipLaunchKernelGGL(k_resolve_plain_filter, dim3(pgrid), dim3(WAVE),
+                               0, s->stream, s->d_payload, s->d_sidecar,
+                               s->d_blocks, s->n_blocks, fs, sl,
+                               s->d_preds + (int64_t)sl * s->n_blocks,
+                               s->d_pred_bm, s->d_plain_ctr, s->n_plain_host);
+            HIP_TRY(s, hipGetLastError());
+        }
+    }
+    return launch_scan(s, min_ts, max_ts, s->d_preds, fs.n_slots);
 }
 
 extern "C" double bydb_last_consume_ms(bydb_session *s) { return s->last_ms; }

@@ -175,6 +175,80 @@ int bydb_consume_multi(bydb_session *s, int64_t min_ts, int64_t max_ts,
                        const uint8_t *const *preds, const uint64_t *pred_lens,
                        int n_preds);
 
+/* ---- tag filter operators (measure query conditions) ----
+ * The reference builds one TagFilter per modelv1.Condition in parseFilter
+ * (pkg/query/logical/tag_filter.go:144-193).  The eight operators that
+ * apply to scalar string and int tags are pushed down here; HAVING,
+ * NOT_HAVING (array tags) and MATCH (analyzed text) stay with the host.
+ * BYDB_OP_* carry the numeric values of modelv1.Condition.BinaryOp
+ * (api/proto/banyandb/model/v1/query.proto:54-65).
+ *
+ * A tag value is a byte string or nil.  A nil dictionary entry / plain row
+ * has stored length 0; a block with no column on the slot is all-nil.  The
+ * empty string is a real value, distinct from nil.
+ *
+ *   op      matches a value v                                  nil row
+ *   EQ      bytes(v) == literal  (eqTag.Match, :426-432;       false
+ *           nullLiteral.Equal is false)
+ *   NE      notTag(eqTag): !EQ   (:168, :370-376)              TRUE
+ *   IN      v equals any list element (inTag.Match :405-411,   false
+ *           BelongTo, expr_literal.go:84-92, 260-268)
+ *   NOT_IN  notTag(inTag): !IN   (:189)                        TRUE
+ *   GT      c < 0    with c = literal.Compare(v)               false
+ *   GE      c <= 0   (rangeTag.Match, :465-503; Compare        false
+ *   LT      c > 0     returns ok=false on nil, which           false
+ *   LE      c >= 0    rejects the row)                         false
+ *
+ * Compare, string type: strings.Compare — bytewise lexicographic, a proper
+ * prefix sorts first (expr_literal.go:241-246).  Compare, int type:
+ * int(lit - val) with Go's WRAPPING int64 subtraction
+ * (expr_literal.go:65-70): both 8-byte sign-flip cells (convert/
+ * number.go:33-46) are decoded to int64, subtracted in uint64, and the
+ * sign of the difference decides — so pairs more than 2^63 apart take the
+ * reference's wrapped answer, not the mathematical one.  A stored value
+ * that is not 8 bytes long never matches an int range.  Int literals are
+ * passed as the stored 8-byte cell; EQ/NE/IN/NOT_IN compare cells by
+ * bytes for both tag types.
+ *
+ * Conditions are ANDed (andLogicalNode); several may target one slot
+ * (200 <= code < 300 is two).  OR across conditions is out of scope: a
+ * host with an OR tree keeps that query on its CPU path. */
+enum {
+    BYDB_OP_EQ = 1,
+    BYDB_OP_NE = 2,
+    BYDB_OP_LT = 3,
+    BYDB_OP_GT = 4,
+    BYDB_OP_LE = 5,
+    BYDB_OP_GE = 6,
+    BYDB_OP_IN = 9,
+    BYDB_OP_NOT_IN = 10,
+};
+
+/* tag type of a condition's literal(s) — databasev1.TagType scalar kinds */
+enum { BYDB_TAG_STRING = 1, BYDB_TAG_INT = 2 };
+
+#define BYDB_FILTER_MAX_CONDS 8      /* conditions per call */
+#define BYDB_FILTER_MAX_VALUES 4096  /* literal values per call, all conds */
+
+typedef struct {
+    int32_t slot;                /* block tag slot 0-2 */
+    int32_t op;                  /* BYDB_OP_* */
+    int32_t tag_type;            /* BYDB_TAG_* */
+    uint32_t n_values;           /* IN / NOT_IN: >= 1; every other op: 1 */
+    const uint8_t *values;       /* concatenated literal bytes */
+    const uint64_t *value_offs;  /* n_values + 1 prefix offsets into values */
+} bydb_tag_cond;
+
+/* Scan with ANDed tag conditions.  Same asynchronous and sticky-error
+ * contract as the equality entry points above; n_conds == 0 is an
+ * unfiltered scan.  BYDB_ERR_BAD_ARG (session stays usable) when n_conds
+ * is outside 0..BYDB_FILTER_MAX_CONDS, a slot / op / tag type is unknown,
+ * IN / NOT_IN carry no value, another op carries other than exactly one,
+ * an int-typed GT / GE / LT / LE literal is not 8 bytes, or the call
+ * carries more than BYDB_FILTER_MAX_VALUES values in total. */
+int bydb_consume_filter(bydb_session *s, int64_t min_ts, int64_t max_ts,
+                        const bydb_tag_cond *conds, int n_conds);
+
 /* ---- finalize + emit (Finalize/NextBatch) ----
  * Syncs the stream, downloads partials and finalises per-group results
  * (MEAN = sum/count with the >=1 clamp; float64 restore per float.go).

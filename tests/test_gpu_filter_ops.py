@@ -1,0 +1,339 @@
+"""GPU parity for the tag filter operators (EQ, NE, LT, LE, GT, GE, IN,
+NOT_IN — bydb_consume_filter) against the reference evaluator in
+tests/filter_ref.py, folded over the rows each test generated.  int64
+sum / count / min / max are bit-exact; the float64 case checks min / max
+exactly and the sum to rel 1e-9 (the project's stated tolerance)."""
+import ctypes as C
+import math
+import random
+
+import pytest
+
+import banyandb_amd as ba
+from banyandb_amd import (PartBuilder, Session, TagCond, TagCondC, VT_INT64,
+                          VT_FLOAT64, AGG_SUM, AGG_COUNT, AGG_MIN, AGG_MAX,
+                          OP_EQ, OP_NE, OP_LT, OP_GT, OP_LE, OP_GE, OP_IN,
+                          OP_NOT_IN, TAG_STRING, TAG_INT, INT64_MIN,
+                          INT64_MAX)
+import filter_ref as fr
+import filter_cases as fc
+from helpers import oracle_scan
+
+pytestmark = pytest.mark.gpu
+
+FUNCS = [AGG_SUM, AGG_COUNT, AGG_MIN, AGG_MAX]
+T0, MS, ENVS = fc.T0, fc.MS, fc.ENVS
+BAD_ARG = -3
+
+
+def clamp_args(scen):
+    return (INT64_MIN if scen.min_ts is None else scen.min_ts,
+            INT64_MAX if scen.max_ts is None else scen.max_ts)
+
+
+def gpu_filter(builder, conds, vtype=VT_INT64, lo=INT64_MIN, hi=INT64_MAX,
+               float_exp=0):
+    s = Session(0)
+    s.upload_part(builder)
+    s.configure(vtype, FUNCS, float_exp=float_exp)
+    s.consume_filter(conds, lo, hi)
+    g = s.finalize()[0]
+    s.close()
+    return g
+
+
+def assert_i64(g, ref, what=""):
+    print(what, "gpu", (g.count, g.sum_i), "ref", (ref.count, ref.sum_i))
+    assert g.count == ref.count, what
+    assert g.sum_i == ref.sum_i, what
+    if ref.count:
+        assert (g.min_i, g.max_i) == (ref.min, ref.max), what
+
+
+@pytest.mark.parametrize("name,make,expect", fc.CASES, ids=fc.CASE_IDS)
+def test_filter_parity(name, make, expect):
+    scen = make()
+    lo, hi = clamp_args(scen)
+    ref = fr.fold(scen.blocks, scen.conds, scen.min_ts, scen.max_ts)
+    b = scen.builder()
+    if scen.float_vals:
+        g = gpu_filter(b, scen.conds, VT_FLOAT64, lo, hi,
+                       float_exp=b.blocks()[0].exp)
+        print(name, "gpu", (g.count, g.sum_f), "ref", (ref.count, ref.sum_f))
+        assert g.count == ref.count > 0
+        assert (g.min_f, g.max_f) == (ref.min, ref.max)
+        assert math.isclose(g.sum_f, ref.sum_f, rel_tol=1e-9)
+        return
+    g = gpu_filter(b, scen.conds, VT_INT64, lo, hi)
+    assert_i64(g, ref, name)
+    if expect == fc.NONE:
+        assert g.count == 0
+    if expect == fc.ALL:
+        assert g.count == scen.n_rows
+
+
+# ---- EQ cross-check against the old path and the oracle ----
+# (builders copied from test_gpu_predicate.py)
+def entity_tag_part(rng, n_series=8, n=3000):
+    """Entity tag: constant per series (the uniform fast path)."""
+    b = PartBuilder()
+    for sid in range(n_series):
+        ts = [T0 + i * MS for i in range(n)]
+        b.add_block_i64(sid + 1, ts, [1] * n,
+                        [rng.randint(-10**9, 10**9) for _ in range(n)])
+        b.set_block_tag([ENVS[sid % 4]] * n)
+    return b
+
+
+def rowvary_tag_part(rng, n_series=8, n=2000):
+    """Row-varying tag: multi-run RLE inside each block."""
+    b = PartBuilder()
+    for sid in range(n_series):
+        ts = [T0 + i * MS for i in range(n)]
+        b.add_block_i64(sid + 1, ts, [1] * n,
+                        [rng.randint(-10**9, 10**9) for _ in range(n)])
+        tags = []
+        while len(tags) < n:
+            run = min(rng.randint(1, 200), n - len(tags))
+            v = ENVS[rng.randrange(4)] if rng.random() > 0.1 else None
+            tags.extend([v] * run)
+        b.set_block_tag(tags)
+    return b
+
+
+@pytest.mark.parametrize("part", [entity_tag_part, rowvary_tag_part],
+                         ids=["entity", "rowvarying"])
+def test_eq_equals_old_consume_and_oracle(part):
+    b = part(random.Random(2101))
+    s = Session(0)
+    s.upload_part(b)
+    s.configure(VT_INT64, FUNCS)
+    seen = 0
+    for pred in (b"prod", b"dev", b"qa", b"absent"):
+        orc = oracle_scan(b, VT_INT64, pred=pred)[0]
+        s.reset()
+        s.consume(preds=[pred])
+        old = s.finalize()[0]
+        s.reset()
+        s.consume_filter([TagCond(0, OP_EQ, [pred])])
+        new = s.finalize()[0]
+        for g in (old, new):
+            assert (g.count, g.sum_i) == (orc.count, orc.sum_i), pred
+            if orc.count:
+                assert (g.min_i, g.max_i) == (orc.min_i, orc.max_i), pred
+        seen += orc.count
+    s.close()
+    assert seen > 0
+
+
+# ---- verdict shortcuts ----
+def test_ne_absent_equals_unfiltered_scan():
+    scen = fc.ne_absent_case()
+    b = scen.builder()
+    s = Session(0)
+    s.upload_part(b)
+    s.configure(VT_INT64, FUNCS)
+    s.consume()
+    plain = s.finalize()[0]
+    s.reset()
+    s.consume_filter(scen.conds)
+    ne = s.finalize()[0]
+    s.reset()
+    s.consume_filter([])          # n_conds == 0: unfiltered too
+    none = s.finalize()[0]
+    s.close()
+    for g in (ne, none):
+        assert (g.count, g.sum_i, g.min_i, g.max_i) == \
+            (plain.count, plain.sum_i, plain.min_i, plain.max_i)
+    assert plain.count == scen.n_rows
+
+
+def test_block_without_column_negated_selects_all_eq_none():
+    blocks = fc.no_column_part(random.Random(1803))
+    tagged, bare = blocks
+    b = fc.Scenario(blocks, []).builder()
+    for op, lits in ((OP_NE, [b"prod"]), (OP_NOT_IN, [b"prod", b"qa"])):
+        conds = [TagCond(0, op, lits)]
+        g = gpu_filter(b, conds)
+        assert_i64(g, fr.fold(blocks, conds), f"op {op}")
+        # every row of the bare block is selected
+        assert g.count == len(bare.ts) + fr.fold([tagged], conds).count
+    for op, lits in ((OP_EQ, [b"prod"]), (OP_IN, [b"prod"]),
+                     (OP_GE, [b""]), (OP_LE, [b"zzz"])):
+        conds = [TagCond(0, op, lits)]
+        g = gpu_filter(b, conds)
+        want = fr.fold([tagged], conds)     # nothing from the bare block
+        assert want.count > 0
+        assert_i64(g, want, f"op {op}")
+    # negated AND positive on the bare block's slot: positive wins
+    conds = [TagCond(0, OP_NE, [b"dev"]), TagCond(0, OP_GE, [b"a"])]
+    assert_i64(gpu_filter(b, conds), fr.fold([tagged], conds), "mixed")
+
+
+# ---- grouped sessions ----
+def _grouped_blocks(rng, plain_second):
+    blocks = []
+    for sid in range(4):
+        n = 2000
+        second = (fc.plain_col(rng, n) if plain_second else
+                  fc.runs(rng, n, [fc.icell(c) for c in fc.CODES],
+                          maxrun=70, nil_p=0.1))
+        blocks.append(fc.Blk(sid + 1, fc.ts_of(n), fc.ivals(rng, n),
+                             [fc.runs(rng, n, ENVS, nil_p=0.1), second]))
+    return blocks
+
+
+def _run_grouped(blocks, conds, domain):
+    s = Session(0)
+    s.upload_part(fc.Scenario(blocks, []).builder())
+    s.configure_by_tag(VT_INT64, FUNCS, 0, domain)
+    s.consume_filter(conds)
+    gs = s.finalize()
+    s.close()
+    refs = fr.fold_by_tag(blocks, conds, 0, domain)
+    unfiltered = fr.fold_by_tag(blocks, [], 0, domain)
+    assert 0 < sum(r.count for r in refs) < sum(r.count for r in unfiltered)
+    for gi, (g, ref) in enumerate(zip(gs, refs)):
+        assert_i64(g, ref, f"group {gi}")
+
+
+def test_grouped_rowvarying_with_range_on_second_dict_slot():
+    blocks = _grouped_blocks(random.Random(2201), plain_second=False)
+    _run_grouped(blocks, [TagCond(1, OP_GE, [0], TAG_INT),
+                          TagCond(1, OP_LT, [500], TAG_INT)],
+                 [b"prod", b"dev", b"qa"])
+
+
+def test_grouped_rowvarying_with_not_in_on_plain_slot():
+    blocks = _grouped_blocks(random.Random(2202), plain_second=True)
+    lits = [b"u%d" % i for i in range(0, 400, 3)] + [b""]
+    _run_grouped(blocks, [TagCond(1, OP_NOT_IN, lits)],
+                 [b"prod", b"dev", b"qa"])
+
+
+def test_block_code_grouped_session():
+    rng = random.Random(2203)
+    scen = fc.Scenario(fc.rowvary(rng, ENVS, n_series=6), [])
+    b = PartBuilder()
+    for i, blk in enumerate(scen.blocks):
+        b.add_block_i64(blk.sid, blk.ts, [1] * len(blk.ts), blk.vals,
+                        group_code=i % 3)
+        b.set_block_tag(blk.tags[0])
+    conds = [TagCond(0, OP_NOT_IN, [b"prod", b"qa"])]
+    s = Session(0)
+    s.upload_part(b)
+    s.configure(VT_INT64, FUNCS, n_groups=3)
+    s.consume_filter(conds)
+    gs = s.finalize()
+    s.close()
+    for gi, g in enumerate(gs):
+        ref = fr.fold([blk for i, blk in enumerate(scen.blocks)
+                       if i % 3 == gi], conds)
+        assert ref.count > 0
+        assert_i64(g, ref, f"group {gi}")
+
+
+# ---- error contract ----
+def _raw_cond(slot, op, tag_type, values, n_values=None):
+    blob = b"".join(values)
+    offs = [0]
+    for v in values:
+        offs.append(offs[-1] + len(v))
+    buf = (C.c_uint8 * max(len(blob), 1)).from_buffer_copy(blob or b"\0")
+    oa = (C.c_uint64 * len(offs))(*offs)
+    c = TagCondC(slot, op, tag_type,
+                 len(values) if n_values is None else n_values,
+                 C.cast(buf, C.POINTER(C.c_uint8)), oa)
+    return c, (buf, oa)
+
+
+def test_argument_limits_are_bad_arg_and_session_survives():
+    scen = fc.str_op_case(1000, OP_EQ, [b"prod"])()
+    good = [TagCond(0, OP_EQ, [b"prod"])]
+    want = fr.fold(scen.blocks, good)
+    s = Session(0)
+    s.upload_part(scen.builder())
+    s.configure(VT_INT64, FUNCS)
+    lib = ba.lib()
+
+    def call(raw, n=None):
+        arr = (TagCondC * max(len(raw), 1))(*[r[0] for r in raw])
+        return lib.bydb_consume_filter(s._h, INT64_MIN, INT64_MAX, arr,
+                                       len(raw) if n is None else n)
+
+    cell = ba.i64_tag_cell(5)
+    one = _raw_cond(0, OP_EQ, TAG_STRING, [b"prod"])
+    bad = {
+        "n_conds 9": ([one] * 9, None),
+        "n_conds -1": ([one], -1),
+        "IN without values": ([_raw_cond(0, OP_IN, TAG_STRING, [])], None),
+        "NOT_IN without values": ([_raw_cond(0, OP_NOT_IN, TAG_STRING, [])],
+                                  None),
+        "EQ with two values": ([_raw_cond(0, OP_EQ, TAG_STRING,
+                                          [b"a", b"b"])], None),
+        "GE with no value": ([_raw_cond(0, OP_GE, TAG_STRING, [])], None),
+        "int LT with a 3-byte literal": ([_raw_cond(0, OP_LT, TAG_INT,
+                                                    [b"abc"])], None),
+        "int GE with a 9-byte literal": ([_raw_cond(0, OP_GE, TAG_INT,
+                                                    [cell + b"x"])], None),
+        "4097 values": ([_raw_cond(0, OP_IN, TAG_STRING,
+                                   [b"v%d" % i for i in range(4097)])], None),
+        "4097 values over two conds": (
+            [_raw_cond(0, OP_IN, TAG_STRING, [b"v%d" % i for i in range(4096)]),
+             one], None),
+        "slot 3": ([_raw_cond(3, OP_EQ, TAG_STRING, [b"prod"])], None),
+        "unknown op": ([_raw_cond(0, 7, TAG_STRING, [b"prod"])], None),
+        "unknown tag type": ([_raw_cond(0, OP_EQ, 9, [b"prod"])], None),
+    }
+    for what, (raw, n) in bad.items():
+        assert call(raw, n) == BAD_ARG, what
+        assert lib.bydb_last_error(s._h), what
+        # still usable: the next good call folds the right answer
+        s.reset()
+        s.consume_filter(good)
+        assert_i64(s.finalize()[0], want, f"after {what}")
+    # the limits themselves are accepted: 8 conditions, 4096 values
+    s.reset()
+    s.consume_filter(good * 8)
+    assert_i64(s.finalize()[0], want, "8 conds")
+    big = [TagCond(0, OP_IN, [b"prod"] + [b"v%d" % i for i in range(4095)])]
+    s.reset()
+    s.consume_filter(big)
+    assert_i64(s.finalize()[0], want, "4096 values")
+    s.close()
+
+
+# ---- randomised leg ----
+@pytest.mark.parametrize("chunk", range(4))
+def test_randomised_scenarios(chunk):
+    for seed in range(3000 + chunk * 10, 3000 + chunk * 10 + 10):
+        scen = fc.random_scenario(seed)
+        lo, hi = clamp_args(scen)
+        ref = fr.fold(scen.blocks, scen.conds, scen.min_ts, scen.max_ts)
+        try:
+            g = gpu_filter(scen.builder(), scen.conds, VT_INT64, lo, hi)
+            assert_i64(g, ref, f"seed {seed}")
+        except Exception:
+            print(f"FAILING SEED {seed}: fc.random_scenario({seed})")
+            raise
+
+
+# ---- the pure-C consumer ----
+def test_c_consumer_runs_filtered_scan(tmp_path):
+    """tools/cabi_filter_check.c: one filtered scan through the header
+    alone, checked against its own host loop."""
+    import os
+    import subprocess
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "cabi_filter_check")
+    subprocess.run(
+        ["gcc", "-std=c99", "-Wall", "-Werror", "-I",
+         os.path.join(repo, "include"),
+         os.path.join(repo, "tools", "cabi_filter_check.c"),
+         "-L", os.path.join(repo, "banyandb_amd"), "-lbydb_gpu",
+         "-Wl,-rpath," + os.path.join(repo, "banyandb_amd"), "-o", exe],
+        check=True)
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(p.stdout, p.stderr)
+    assert p.returncode == 0, p.stderr + p.stdout
+    assert "filter consumer OK" in p.stdout
