@@ -830,6 +830,161 @@ __device__ inline uint32_t domain_lookup(const GroupDomain *d, const uint8_t *v,
     return GID_NONE;
 }
 
+// ---- tag stream openers shared by every resolve kernel ----
+// offset / length of a block's tag stream on one slot
+__device__ __forceinline__ void tag_slot(const bydb_block_desc *bd, int slot,
+                                         uint64_t *off, uint64_t *len) {
+    *off = slot == 0 ? bd->tag_off : slot == 1 ? bd->tag2_off : bd->tag3_off;
+    *len = slot == 0 ? bd->tag_len : slot == 1 ? bd->tag2_len : bd->tag3_len;
+}
+
+// big-endian width-typed length i of a lengths list (bytes.go:205-235);
+// the stored value is len+1, 0 marks a nil value
+__device__ __forceinline__ uint64_t be_len(const uint8_t *lens, uint64_t i,
+                                           uint32_t wbytes) {
+    uint64_t v = 0;
+    for (uint32_t b = 0; b < wbytes; b++) v = (v << 8) | lens[i * wbytes + b];
+    return v;
+}
+
+__device__ __forceinline__ uint32_t len_width_bytes(uint8_t wt) {
+    return wt == 0 ? 1 : wt == 1 ? 2 : wt == 2 ? 4 : 8;
+}
+
+#define TS_NIL 0     // block has no column on the slot: every row nil
+#define TS_PLAIN 1   // plain (non-dictionary) column, see plain_open
+#define TS_DICT 2
+#define TS_ERR 3     // unparseable on device
+
+struct DictStream {
+    const uint8_t *base;   // payload or sidecar; bit0 is relative to it
+    const uint8_t *lens;   // `count` lengths (be_len), wbytes each
+    const uint8_t *vals;   // value bytes, back to back
+    uint64_t count;        // dictionary values
+    uint64_t bit0;         // bit offset of the first packed RLE entry
+    uint32_t wbytes;
+    uint32_t nentries;     // packed entries, 2 per run: code, count
+    uint32_t width;        // bits per packed entry
+    bool in_sidecar;       // host-normalized stream (TAG_SIDECAR_BIT)
+};
+
+// Classify a block's tag stream on one slot; for TS_DICT parse the stream
+// header: [ENC_DICTIONARY][varuint count (int.go:152-199)][lengths section]
+// [values section][32b entry count][8b width][entries...] (bit-packed
+// MSB-first).  base / in_sidecar are set for every kind but TS_NIL.
+__device__ int tag_open(const uint8_t *__restrict__ payload,
+                        const uint8_t *__restrict__ sidecar,
+                        const bydb_block_desc *__restrict__ bd, int slot,
+                        DictStream *ds) {
+    uint64_t toff, tlen;
+    tag_slot(bd, slot, &toff, &tlen);
+    if (tlen == 0) return TS_NIL;
+    ds->in_sidecar = (toff & TAG_SIDECAR_BIT) != 0;
+    ds->base = ds->in_sidecar ? sidecar : payload;
+    const uint8_t *p = ds->base + (toff & ~TAG_SIDECAR_BIT);
+    const uint8_t *end = p + tlen;
+    if (*p == BYDB_ENC_PLAIN) return TS_PLAIN;
+    if (*p != BYDB_ENC_DICTIONARY) return TS_ERR;
+    p++;
+    uint64_t count = 0;
+    unsigned sh = 0;
+    while (p < end) {
+        uint8_t c = *p++;
+        count |= (uint64_t)(c & 0x7f) << sh;
+        if (c < 0x80) break;
+        sh += 7;
+    }
+    ds->count = count;
+    uint64_t ll = 0;
+    const uint8_t *lens_blk = dict_section(p, end, &ll);
+    if (!lens_blk) return TS_ERR;
+    uint64_t vl = 0;
+    ds->vals = dict_section(lens_blk + ll, end, &vl);
+    if (!ds->vals) return TS_ERR;
+    ds->wbytes = len_width_bytes(lens_blk[0]);
+    ds->lens = lens_blk + 1;
+    uint64_t hdr = ((uint64_t)(ds->vals + vl - ds->base)) * 8;
+    ds->nentries = (uint32_t)rd_bits_be(ds->base, hdr, 32);
+    ds->width = ds->nentries ? (uint32_t)rd_bits_be(ds->base, hdr + 32, 8) : 0;
+    ds->bit0 = hdr + 40;
+    return TS_DICT;
+}
+
+// the rle_bit_off a PredBlock / GroupBlock carries for this dictionary
+__device__ __forceinline__ uint64_t dict_rle_bit_off(const DictStream &ds) {
+    return ds.bit0 | (ds.in_sidecar ? TAG_SIDECAR_BIT : 0);
+}
+
+// Single-run check: one (code, count) pair whose count covers the whole
+// block.  Returns that run's code, or -1 for a row-varying block.
+__device__ __forceinline__ int64_t dict_uniform_code(
+    const DictStream &ds, const bydb_block_desc *bd) {
+    if (ds.nentries != 2) return -1;
+    uint64_t code = rd_bits_be(ds.base, ds.bit0, ds.width);
+    uint64_t cnt = rd_bits_be(ds.base, ds.bit0 + ds.width, ds.width);
+    return cnt >= bd->count ? (int64_t)code : -1;
+}
+
+struct PlainStream {
+    const uint8_t *lens;   // `n` lengths (be_len), wbytes each
+    const uint8_t *vals;   // value bytes, back to back
+    uint64_t n;            // rows
+    uint32_t wbytes;
+};
+
+// Header of a host-normalized plain stream: [ENC_PLAIN][u32le n][wt]
+// [lens BE][payload].  False when n disagrees with the block's row count.
+__device__ __forceinline__ bool plain_open(
+    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
+    const bydb_block_desc *__restrict__ bd, int slot, PlainStream *ps) {
+    uint64_t toff, tlen;
+    tag_slot(bd, slot, &toff, &tlen);
+    const uint8_t *p = (toff & TAG_SIDECAR_BIT)
+                           ? sidecar + (toff & ~TAG_SIDECAR_BIT)
+                           : payload + toff;
+    p++;  // ENC_PLAIN
+    ps->n = (uint64_t)p[0] | ((uint64_t)p[1] << 8) | ((uint64_t)p[2] << 16) |
+            ((uint64_t)p[3] << 24);
+    ps->wbytes = len_width_bytes(p[4]);
+    ps->lens = p + 5;
+    ps->vals = ps->lens + ps->n * ps->wbytes;
+    return ps->n == (uint64_t)bd->count;
+}
+
+// one lane's row of a 64-row chunk of a plain stream
+struct PlainRow {
+    bool valid;     // row < n
+    uint64_t lp1;   // stored length: len+1, 0 = nil row
+    uint64_t vlen;
+    uint64_t off;   // value offset in PlainStream::vals
+};
+
+// Rows [base, base+64) of a plain stream, one per lane: a wave prefix scan
+// over the value lengths gives the payload offsets.  *carry is the payload
+// bytes consumed by the chunks before (0 at base 0) and is advanced.  The
+// whole wave calls this together.
+__device__ __forceinline__ PlainRow plain_chunk(const PlainStream &ps,
+                                                uint64_t base, int lane,
+                                                uint64_t *carry) {
+    PlainRow r;
+    uint64_t row = base + (uint64_t)lane;
+    r.valid = row < ps.n;
+    r.lp1 = r.valid ? be_len(ps.lens, row, ps.wbytes) : 0;
+    r.vlen = r.lp1 ? r.lp1 - 1 : 0;
+    uint64_t incl = wave_incl_scan(r.vlen, lane);
+    r.off = *carry + incl - r.vlen;
+    *carry += readlane64(incl, WAVE - 1);
+    return r;
+}
+
+// Claim the next per-stream arena slot (bitmap words / run pairs) for the
+// block this wave resolves; every lane gets the id.
+__device__ __forceinline__ uint32_t claim_stream_slot(uint32_t *ctr, int lane) {
+    uint32_t slot_id = 0;
+    if (lane == 0) slot_id = atomicAdd(ctr, 1u);
+    return (uint32_t)__shfl((int)slot_id, 0);
+}
+
 // one thread per block: parse the tag dictionary, map codes to gids
 __global__ void k_resolve_groups(const uint8_t *__restrict__ payload,
                                  const uint8_t *__restrict__ sidecar,
@@ -841,84 +996,42 @@ __global__ void k_resolve_groups(const uint8_t *__restrict__ payload,
     int64_t bi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (bi >= n_blocks) return;
     const bydb_block_desc *bd = &blocks[bi];
-    uint64_t toff = slot == 0 ? bd->tag_off : slot == 1 ? bd->tag2_off : bd->tag3_off;
-    uint64_t tlen = slot == 0 ? bd->tag_len : slot == 1 ? bd->tag2_len : bd->tag3_len;
     GroupBlock gb;
     gb.uniform_gid = GID_NONE;
     gb.map_off = map_base + (uint32_t)(bi * 256);
     gb.rle_bit_off = 0; gb.nentries = 0; gb.width = 0; gb.err = 0;
     gb._p[0] = gb._p[1] = 0;
-    if (tlen == 0) { out[bi] = gb; return; }
-    const bool in_sidecar = (toff & TAG_SIDECAR_BIT) != 0;
-    const uint8_t *base = in_sidecar ? sidecar : payload;
-    const uint8_t *p = base + (toff & ~TAG_SIDECAR_BIT);
-    const uint8_t *end = p + tlen;
-    if (*p != BYDB_ENC_DICTIONARY) {
-        if (*p == BYDB_ENC_PLAIN) {
-            // plain (>256-distinct) column: per-row gids are resolved by
-            // the follow-up wave kernel (k_resolve_plain_groups) into
-            // (gid,count) run pairs; width 0xFF + nentries 0 marks
-            // "pending" and the scan errors loudly if it stays that way
-            gb.width = 0xFF;
-            gb.uniform_gid = GID_VARYING;
-            gb.nentries = 0;
-            out[bi] = gb;
-            return;
-        }
-        gb.err = 1;
-        out[bi] = gb;
-        return;
+    DictStream ds;
+    int kind = tag_open(payload, sidecar, bd, slot, &ds);
+    if (kind == TS_PLAIN) {
+        // plain (>256-distinct) column: per-row gids are resolved by the
+        // follow-up wave kernel (k_resolve_plain_groups) into (gid,count)
+        // run pairs; width 0xFF + nentries 0 marks "pending" and the scan
+        // errors loudly if it stays that way
+        gb.width = 0xFF;
+        gb.uniform_gid = GID_VARYING;
     }
-    p++;
-    uint64_t count = 0;
-    unsigned sh = 0;
-    while (p < end) {
-        uint8_t c = *p++;
-        count |= (uint64_t)(c & 0x7f) << sh;
-        if (c < 0x80) break;
-        sh += 7;
-    }
-    uint64_t ll = 0;
-    const uint8_t *lens_blk = dict_section(p, end, &ll);
-    if (!lens_blk) { gb.err = 1; out[bi] = gb; return; }
-    p = lens_blk + ll;
-    uint64_t vl = 0;
-    const uint8_t *vals = dict_section(p, end, &vl);
-    if (!vals) { gb.err = 1; out[bi] = gb; return; }
-    p = vals + vl;
-    uint8_t wt = lens_blk[0];
-    uint32_t wbytes = wt == 0 ? 1 : wt == 1 ? 2 : wt == 2 ? 4 : 8;
-    const uint8_t *lp = lens_blk + 1;
+    if (kind == TS_ERR) gb.err = 1;
+    if (kind != TS_DICT) { out[bi] = gb; return; }
     uint64_t voff = 0;
     uint16_t *map = map_arena + gb.map_off;
-    for (uint64_t v = 0; v < count && v < 256; v++) {
-        uint64_t alen = 0;
-        for (uint32_t b = 0; b < wbytes; b++) alen = (alen << 8) | lp[v * wbytes + b];
-        uint32_t g = GID_NONE;
-        if (alen > 0) {
-            uint64_t vlen = alen - 1;
-            g = domain_lookup(&dom, vals + voff, vlen);
-            voff += vlen;
-        }
+    for (uint64_t v = 0; v < ds.count && v < 256; v++) {
+        uint64_t alen = be_len(ds.lens, v, ds.wbytes);
+        uint64_t vlen = alen ? alen - 1 : 0;
+        uint32_t g = alen ? domain_lookup(&dom, ds.vals + voff, vlen) : GID_NONE;
+        voff += vlen;
         map[v] = g == GID_NONE ? 0xFFFFu : (uint16_t)g;
     }
-    uint64_t bit0 = ((uint64_t)(p - base)) * 8;
-    uint32_t nentries = (uint32_t)rd_bits_be(base, bit0, 32);
-    uint32_t width = nentries ? (uint32_t)rd_bits_be(base, bit0 + 32, 8) : 0;
-    gb.nentries = nentries;
-    gb.width = (uint8_t)width;
-    gb.rle_bit_off = (bit0 + 40) | (in_sidecar ? TAG_SIDECAR_BIT : 0);
-    if (nentries == 2) {
-        uint64_t code = rd_bits_be(base, bit0 + 40, width);
-        uint64_t cnt = rd_bits_be(base, bit0 + 40 + width, width);
-        if (cnt >= bd->count) {
-            uint16_t m = map[code < 256 ? code : 0];
-            gb.uniform_gid = m == 0xFFFFu ? GID_NONE : m;
-            out[bi] = gb;
-            return;
-        }
+    gb.nentries = ds.nentries;
+    gb.width = (uint8_t)ds.width;
+    gb.rle_bit_off = dict_rle_bit_off(ds);
+    int64_t code = dict_uniform_code(ds, bd);
+    if (code >= 0) {
+        uint16_t m = map[code < 256 ? code : 0];
+        gb.uniform_gid = m == 0xFFFFu ? GID_NONE : m;
+    } else {
+        gb.uniform_gid = GID_VARYING;
     }
-    gb.uniform_gid = GID_VARYING;
     out[bi] = gb;
 }
 
@@ -944,26 +1057,13 @@ __global__ __launch_bounds__(WAVE) void k_resolve_plain_groups(
         GroupBlock gb = out[bi];
         if (gb.width != 0xFF || gb.err) continue;
         const bydb_block_desc *bd = &blocks[bi];
-        uint64_t toff = slot == 0 ? bd->tag_off
-                                  : slot == 1 ? bd->tag2_off : bd->tag3_off;
-        const uint8_t *p = (toff & TAG_SIDECAR_BIT)
-                               ? sidecar + (toff & ~TAG_SIDECAR_BIT)
-                               : payload + toff;
-        p++;  // ENC_PLAIN
-        uint64_t n = (uint64_t)p[0] | ((uint64_t)p[1] << 8) |
-                     ((uint64_t)p[2] << 16) | ((uint64_t)p[3] << 24);
-        p += 4;
-        uint8_t wt = *p++;
-        uint32_t wbytes = wt == 0 ? 1 : wt == 1 ? 2 : wt == 2 ? 4 : 8;
-        const uint8_t *lens = p;
-        const uint8_t *vals = lens + n * wbytes;
-        if (n != (uint64_t)bd->count) {
+        PlainStream ps;
+        if (!plain_open(payload, sidecar, bd, slot, &ps)) {
             if (lane == 0) out[bi].err = 1;
             continue;
         }
-        uint32_t slot_id = 0;
-        if (lane == 0) slot_id = atomicAdd(ctr, 1u);
-        slot_id = (uint32_t)__shfl((int)slot_id, 0);
+        const uint64_t n = ps.n;
+        uint32_t slot_id = claim_stream_slot(ctr, lane);
         if (slot_id >= grun_cap_streams) {
             if (lane == 0) out[bi].err = 1;   // arena exhausted: loud
             continue;
@@ -974,23 +1074,15 @@ __global__ __launch_bounds__(WAVE) void k_resolve_plain_groups(
         int32_t cur_gid = -2;   // no open run yet
         uint32_t cur_cnt = 0;
         for (uint64_t base = 0; base < n; base += WAVE) {
-            uint64_t row = base + (uint64_t)lane;
-            uint64_t lp1 = 0;
-            if (row < n)
-                for (uint32_t b = 0; b < wbytes; b++)
-                    lp1 = (lp1 << 8) | lens[row * wbytes + b];
-            uint64_t vlen = lp1 ? lp1 - 1 : 0;
-            uint64_t incl = wave_incl_scan(vlen, lane);
-            uint64_t myoff = carry_bytes + incl - vlen;
+            PlainRow r = plain_chunk(ps, base, lane, &carry_bytes);
             int32_t g = -1;     // nil or out-of-domain: dropped row
-            if (row < n && lp1) {
-                uint32_t gg = domain_lookup(&dom, vals + myoff, vlen);
+            if (r.valid && r.lp1) {
+                uint32_t gg = domain_lookup(&dom, ps.vals + r.off, r.vlen);
                 g = gg == GID_NONE ? -1 : (int32_t)gg;
             }
             int32_t prev = __shfl_up(g, 1);
             if (lane == 0) prev = cur_gid;
-            bool valid = row < n;
-            bool is_start = valid && g != prev;
+            bool is_start = r.valid && g != prev;
             uint64_t starts = __ballot(is_start);
             uint32_t chunk_rows =
                 (uint32_t)(n - base < WAVE ? n - base : (uint64_t)WAVE);
@@ -1018,7 +1110,6 @@ __global__ __launch_bounds__(WAVE) void k_resolve_plain_groups(
                 cur_gid = __shfl(g, last);
                 cur_cnt = chunk_rows - (uint32_t)last;
             }
-            carry_bytes += readlane64(incl, WAVE - 1);
         }
         if (cur_cnt > 0) {
             if (lane == 0) {
@@ -1045,222 +1136,19 @@ __global__ __launch_bounds__(WAVE) void k_resolve_plain_groups(
     }
 }
 
-// Resolve prepass: one thread per block parses the dictionary header and
-// builds the code mask.  Only plain (<128 B) compress_block sections are
-// parseable on device (bytes.go:291-303); zstd-compressed dictionaries are
-// flagged and surfaced as a device error if a predicate needs them.
-#define PF_CLEAR 0
-#define PF_SKIP 1
-#define PF_WALK 2
-#define PF_ERR 3
-
-// Resolve one predicate slot for one block; returns the slot verdict
-// (PF_CLEAR uniform-match / PF_SKIP miss-or-nil / PF_WALK row-varying /
-// PF_ERR unparseable) and fills *out for the walker path.
-__device__ int resolve_one_pred(const uint8_t *__restrict__ payload,
-                                const uint8_t *__restrict__ sidecar,
-                                const bydb_block_desc *__restrict__ bd,
-                                int slot, const uint8_t *__restrict__ pred,
-                                uint64_t pred_len, PredBlock *out) {
-    uint64_t toff = slot == 0 ? bd->tag_off : slot == 1 ? bd->tag2_off : bd->tag3_off;
-    uint64_t tlen = slot == 0 ? bd->tag_len : slot == 1 ? bd->tag2_len : bd->tag3_len;
-    PredBlock pb;
-    for (int i = 0; i < 4; i++) pb.mask[i] = 0;
-    pb.rle_bit_off = 0; pb.nentries = 0; pb.width = 0;
-    pb.active = 0; pb.err = 0; pb.uniform = 0; pb.plain = 0;
-    pb.disabled = 0;
-    if (pred_len == 0) {     // slot disabled: no constraint
-        pb.disabled = 1;
-        *out = pb;
-        return PF_CLEAR;
-    }
-    if (tlen == 0) { *out = pb; return PF_SKIP; }   // nil tag: never equal
-    const bool in_sidecar = (toff & TAG_SIDECAR_BIT) != 0;
-    const uint8_t *base = in_sidecar ? sidecar : payload;
-    const uint8_t *p = base + (toff & ~TAG_SIDECAR_BIT);
-    const uint8_t *end = p + tlen;
-    if (*p == BYDB_ENC_PLAIN) {
-        // host-normalized plain column: a second pass (k_resolve_plain)
-        // fills this block's match bitmap.  A plain stream that did NOT
-        // go through host normalization (no sidecar bit) cannot be
-        // parsed here — flag it loudly.
-        if (!in_sidecar) { pb.err = 1; *out = pb; return PF_ERR; }
-        pb.active = 1;
-        pb.plain = 1;
-        *out = pb;
-        return PF_WALK;
-    }
-    if (*p != BYDB_ENC_DICTIONARY) { pb.err = 1; *out = pb; return PF_ERR; }
-    p++;
-    pb.active = 1;
-    // varuint count (int.go:152-199)
-    uint64_t count = 0;
-    unsigned sh = 0;
-    while (p < end) {
-        uint8_t c = *p++;
-        count |= (uint64_t)(c & 0x7f) << sh;
-        if (c < 0x80) break;
-        sh += 7;
-    }
-    // lengths block: compress_block(u64list) — plain or host-normalized
-    uint64_t ll = 0;
-    const uint8_t *lens_blk = dict_section(p, end, &ll);
-    if (!lens_blk) { pb.err = 1; *out = pb; return PF_ERR; }
-    p = lens_blk + ll;
-    // values payload block
-    uint64_t vl = 0;
-    const uint8_t *vals = dict_section(p, end, &vl);
-    if (!vals) { pb.err = 1; *out = pb; return PF_ERR; }
-    p = vals + vl;
-    // parse width-typed lengths (bytes.go:205-235)
-    uint8_t wt = lens_blk[0];
-    uint32_t wbytes = wt == 0 ? 1 : wt == 1 ? 2 : wt == 2 ? 4 : 8;
-    const uint8_t *lp = lens_blk + 1;
-    uint64_t voff = 0;
-    for (uint64_t v = 0; v < count && v < 256; v++) {
-        uint64_t alen = 0;
-        for (uint32_t b = 0; b < wbytes; b++) alen = (alen << 8) | lp[v * wbytes + b];
-        if (alen > 0) {
-            uint64_t vlen = alen - 1;
-            if (vlen == pred_len) {
-                bool eq = true;
-                for (uint64_t k = 0; k < vlen; k++)
-                    if (vals[voff + k] != pred[k]) { eq = false; break; }
-                if (eq) pb.mask[(v >> 6) & 3] |= 1ull << (v & 63);
-            }
-            voff += vlen;
-        }
-    }
-    // bit-packed RLE: [32b entry count][8b width][entries...] MSB-first
-    uint64_t bit0 = ((uint64_t)(p - base)) * 8;
-    uint32_t nentries = (uint32_t)rd_bits_be(base, bit0, 32);
-    uint32_t width = nentries ? (uint32_t)rd_bits_be(base, bit0 + 32, 8) : 0;
-    pb.nentries = nentries;
-    pb.width = (uint8_t)width;
-    pb.rle_bit_off = (bit0 + 40) | (in_sidecar ? TAG_SIDECAR_BIT : 0);
-    int verdict = PF_WALK;
-    if (nentries == 2) {
-        uint64_t code = rd_bits_be(base, bit0 + 40, width);
-        uint64_t cnt = rd_bits_be(base, bit0 + 40 + width, width);
-        if (cnt >= bd->count) {
-            pb.uniform = 1;
-            bool match = (pb.mask[(code >> 6) & 3] >> (code & 63)) & 1;
-            verdict = match ? PF_CLEAR : PF_SKIP;
-        }
-    }
-    *out = pb;
-    return verdict;
-}
-
-// One fused launch resolves every predicate slot for a block (the
-// descriptor is read once) and writes the combined flag byte the scan's
-// hot loop prices a non-matching block at:
-//   0 = every predicated slot is uniform-match -> fold unpredicated
-//   1 = some slot misses (uniform non-match or nil tag) -> skip block
-//   2 = some slot is row-varying -> full walker path
-//   3 = unparseable tag stream -> device error
-__global__ void k_resolve_preds(
-    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
-    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
-    const uint8_t *__restrict__ pred_bytes, uint64_t o0, uint64_t l0,
-    uint64_t o1, uint64_t l1, uint64_t o2, uint64_t l2, int n_preds,
-    PredBlock *__restrict__ out, uint8_t *__restrict__ flags,
-    uint32_t *__restrict__ walk_count) {
-    int64_t bi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (bi >= n_blocks) return;
-    const bydb_block_desc *bd = &blocks[bi];
-    const uint64_t offs[3] = {o0, o1, o2};
-    const uint64_t lens[3] = {l0, l1, l2};
-    uint8_t f = PF_CLEAR;
-    for (int sl = 0; sl < n_preds; sl++) {
-        PredBlock pb;
-        int v = resolve_one_pred(payload, sidecar, bd, sl,
-                                 pred_bytes + offs[sl], lens[sl], &pb);
-        out[(int64_t)sl * n_blocks + bi] = pb;
-        if (v == PF_ERR) { f = PF_ERR; break; }
-        if (v == PF_SKIP) { f = PF_SKIP; break; }
-        if (v == PF_WALK) f = PF_WALK;
-    }
-    flags[bi] = f;
-    // walk-block census: lets the heavy scan pass exit immediately when
-    // every predicate verdict is uniform (the dominant entity-tag case)
-    uint64_t wmask = __ballot(f == PF_WALK);
-    if ((threadIdx.x & 63) == 0 && wmask)
-        atomicAdd(walk_count, (uint32_t)__popcll(wmask));
-}
-
-// Second resolve pass for plain (non-dictionary) tag columns: one wave per
-// block evaluates the equality predicate on every row of the normalized
-// stream ([ENC_PLAIN][u32le n][wt][lens BE][payload]) and writes a per-row
-// match bitmap.  The residual-predicate pushdown the reference performs
-// row-by-row on decoded [][]byte (aggregation.go:310 over column.go:410
-// Plain columns) becomes 64 rows per step with a wave prefix-scan over the
-// value lengths for the payload offsets.
-__global__ __launch_bounds__(WAVE) void k_resolve_plain(
-    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
-    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
-    const uint8_t *__restrict__ pred, uint64_t pred_len, int slot,
-    PredBlock *__restrict__ out, uint64_t *__restrict__ bm,
-    uint32_t *__restrict__ ctr) {
-    const int lane = threadIdx.x;
-    for (int64_t bi = blockIdx.x; bi < n_blocks; bi += gridDim.x) {
-        PredBlock pb = out[bi];
-        if (!pb.plain || pb.err) continue;
-        const bydb_block_desc *bd = &blocks[bi];
-        uint64_t toff = slot == 0 ? bd->tag_off
-                                  : slot == 1 ? bd->tag2_off : bd->tag3_off;
-        const uint8_t *p = (toff & TAG_SIDECAR_BIT)
-                               ? sidecar + (toff & ~TAG_SIDECAR_BIT)
-                               : payload + toff;
-        p++;  // ENC_PLAIN
-        uint64_t n = (uint64_t)p[0] | ((uint64_t)p[1] << 8) |
-                     ((uint64_t)p[2] << 16) | ((uint64_t)p[3] << 24);
-        p += 4;
-        uint8_t wt = *p++;
-        uint32_t wbytes = wt == 0 ? 1 : wt == 1 ? 2 : wt == 2 ? 4 : 8;
-        const uint8_t *lens = p;
-        const uint8_t *vals = lens + n * wbytes;
-        if (n != (uint64_t)bd->count || n > (uint64_t)PLAIN_BM_WORDS * 64) {
-            if (lane == 0) out[bi].err = 1;
-            continue;
-        }
-        uint32_t slot_id = 0;
-        if (lane == 0) slot_id = atomicAdd(ctr, 1u);
-        slot_id = (uint32_t)__shfl((int)slot_id, 0);
-        uint64_t w0 = (uint64_t)slot_id * PLAIN_BM_WORDS;
-        uint64_t carry = 0;  // payload bytes consumed by prior chunks
-        for (uint64_t base = 0; base < n; base += WAVE) {
-            uint64_t row = base + (uint64_t)lane;
-            uint64_t lp1 = 0;
-            if (row < n)
-                for (uint32_t b = 0; b < wbytes; b++)
-                    lp1 = (lp1 << 8) | lens[row * wbytes + b];
-            uint64_t vlen = lp1 ? lp1 - 1 : 0;
-            uint64_t incl = wave_incl_scan(vlen, lane);
-            uint64_t myoff = carry + incl - vlen;
-            bool match = false;
-            if (row < n && lp1 && vlen == pred_len) {
-                match = true;
-                for (uint64_t k = 0; k < vlen; k++)
-                    if (vals[myoff + k] != pred[k]) { match = false; break; }
-            }
-            uint64_t word = __ballot(match);
-            if (lane == 0) bm[w0 + (base >> 6)] = word;
-            carry += readlane64(incl, WAVE - 1);
-        }
-        if (lane == 0) out[bi].rle_bit_off = w0;
-    }
-}
-
-// ---------------- tag filter operators ----------------
+// ---------------- tag condition resolve ----------------
 // The reference evaluates a measure query's tag conditions per row through
 // the TagFilter tree parseFilter builds (pkg/query/logical/
-// tag_filter.go:144-193).  The scan above never sees tag values — it
-// consumes PredBlocks and the combined flag byte — so the eight scalar
-// operators only need their own resolve stage: the same two prepasses as
-// the equality path, evaluating every condition of a slot against each
-// dictionary value (or plain row) and ANDing the results into the slot's
-// code mask (or match bitmap).  Match rules (header comment of
+// tag_filter.go:144-193).  The scan never sees tag values — it consumes
+// PredBlocks and the combined flag byte — so one resolve stage serves every
+// consume entry point (equality predicates are its BYDB_OP_EQ case): a
+// one-thread-per-block prepass evaluates every condition of a slot against
+// each dictionary value and ANDs the results into the slot's code mask; a
+// one-wave-per-block prepass does the same per row of a plain column into
+// a match bitmap.  Only plain (<128 B) compress_block sections are
+// parseable on device (bytes.go:291-303); zstd'd dictionaries are
+// host-normalized at part registration, and one that reaches the device
+// anyway is surfaced as a device error.  Match rules (header comment of
 // include/bydb_gpu.h restates them with the full citations):
 //   EQ  bytes equal, nil never (eqTag.Match :426-432)
 //   NE / NOT_IN  notTag over EQ / IN — TRUE on nil (:168, :189, :370-376)
@@ -1271,6 +1159,11 @@ __global__ __launch_bounds__(WAVE) void k_resolve_plain(
 //       (expr_literal.go:65-70, 241-246)
 // Conditions are ANDed (andLogicalNode); OR across conditions is out of
 // scope.
+// Slot verdicts, and the values of the combined per-block flag byte:
+#define PF_CLEAR 0   // every row matches -> fold unpredicated
+#define PF_SKIP 1    // no row matches -> skip block
+#define PF_WALK 2    // row-varying -> full walker path
+#define PF_ERR 3     // unparseable tag stream -> device error
 struct FilterCond {
     GroupDomain set;        // IN / NOT_IN: open-addressing value set
     const uint8_t *lit;     // every other op: the single literal
@@ -1344,23 +1237,22 @@ __device__ bool filter_match(const FilterSet &fs, int slot, const uint8_t *v,
     return true;
 }
 
-// Resolve one conditioned slot of one block (dictionary columns): parse
-// the dictionary header once, evaluate all of the slot's conditions per
-// dictionary value into the code mask.  Verdicts beyond the equality
-// path's uniform CLEAR / SKIP: a mask covering every code the dictionary
-// defines is CLEAR and an empty mask is SKIP even when the block has many
-// runs (NE of an absent value, or a wide range, must not push row-varying
-// blocks onto the walker path); a block without the column is all-nil —
-// CLEAR when every condition of the slot is negated, else SKIP.  A CLEAR
-// slot is marked `disabled` for this block, so a walk forced by another
-// slot treats it as no constraint.
+// Resolve one conditioned slot of one block; fills *out for the walker
+// path and returns the slot verdict.  Dictionary columns: all of the
+// slot's conditions are evaluated per dictionary value into the code mask.
+// A mask covering every code the dictionary defines is CLEAR and an empty
+// mask is SKIP even when the block has many runs (a value the block never
+// holds, NE of an absent value, or a wide range, must not push row-varying
+// blocks onto the walker path); otherwise a single-run block is CLEAR or
+// SKIP by its one code.  A block without the column is all-nil — CLEAR
+// when every condition of the slot is negated, else SKIP.  A CLEAR slot is
+// marked `disabled` for this block, so a walk forced by another slot
+// treats it as no constraint.
 __device__ int resolve_one_filter(const uint8_t *__restrict__ payload,
                                   const uint8_t *__restrict__ sidecar,
                                   const bydb_block_desc *__restrict__ bd,
                                   int slot, const FilterSet &fs,
                                   PredBlock *out) {
-    uint64_t toff = slot == 0 ? bd->tag_off : slot == 1 ? bd->tag2_off : bd->tag3_off;
-    uint64_t tlen = slot == 0 ? bd->tag_len : slot == 1 ? bd->tag2_len : bd->tag3_len;
     PredBlock pb;
     for (int i = 0; i < 4; i++) pb.mask[i] = 0;
     pb.rle_bit_off = 0; pb.nentries = 0; pb.width = 0;
@@ -1371,53 +1263,32 @@ __device__ int resolve_one_filter(const uint8_t *__restrict__ payload,
         *out = pb;
         return PF_CLEAR;
     }
-    if (tlen == 0) {                              // all-nil block
-        if (fs.all_neg[slot]) { pb.disabled = 1; *out = pb; return PF_CLEAR; }
+    DictStream ds;
+    int kind = tag_open(payload, sidecar, bd, slot, &ds);
+    if (kind == TS_NIL) {                         // all-nil block
+        pb.disabled = fs.all_neg[slot];
         *out = pb;
-        return PF_SKIP;
+        return fs.all_neg[slot] ? PF_CLEAR : PF_SKIP;
     }
-    const bool in_sidecar = (toff & TAG_SIDECAR_BIT) != 0;
-    const uint8_t *base = in_sidecar ? sidecar : payload;
-    const uint8_t *p = base + (toff & ~TAG_SIDECAR_BIT);
-    const uint8_t *end = p + tlen;
-    if (*p == BYDB_ENC_PLAIN) {
-        // host-normalized plain column: k_resolve_plain_filter fills the
-        // match bitmap (an unnormalized plain stream is a loud error)
-        if (!in_sidecar) { pb.err = 1; *out = pb; return PF_ERR; }
-        pb.active = 1;
+    // a plain column must be host-normalized: k_resolve_plain_filter fills
+    // its match bitmap (an unnormalized plain stream is a loud error)
+    if (kind == TS_ERR || (kind == TS_PLAIN && !ds.in_sidecar)) {
+        pb.err = 1;
+        *out = pb;
+        return PF_ERR;
+    }
+    pb.active = 1;
+    if (kind == TS_PLAIN) {
         pb.plain = 1;
         *out = pb;
         return PF_WALK;
     }
-    if (*p != BYDB_ENC_DICTIONARY) { pb.err = 1; *out = pb; return PF_ERR; }
-    p++;
-    pb.active = 1;
-    uint64_t count = 0;
-    unsigned sh = 0;
-    while (p < end) {
-        uint8_t c = *p++;
-        count |= (uint64_t)(c & 0x7f) << sh;
-        if (c < 0x80) break;
-        sh += 7;
-    }
-    uint64_t ll = 0;
-    const uint8_t *lens_blk = dict_section(p, end, &ll);
-    if (!lens_blk) { pb.err = 1; *out = pb; return PF_ERR; }
-    p = lens_blk + ll;
-    uint64_t vl = 0;
-    const uint8_t *vals = dict_section(p, end, &vl);
-    if (!vals) { pb.err = 1; *out = pb; return PF_ERR; }
-    p = vals + vl;
-    uint8_t wt = lens_blk[0];
-    uint32_t wbytes = wt == 0 ? 1 : wt == 1 ? 2 : wt == 2 ? 4 : 8;
-    const uint8_t *lp = lens_blk + 1;
     uint64_t voff = 0;
     bool any = false, all = true;
-    for (uint64_t v = 0; v < count && v < 256; v++) {
-        uint64_t alen = 0;
-        for (uint32_t b = 0; b < wbytes; b++) alen = (alen << 8) | lp[v * wbytes + b];
+    for (uint64_t v = 0; v < ds.count && v < 256; v++) {
+        uint64_t alen = be_len(ds.lens, v, ds.wbytes);
         uint64_t vlen = alen ? alen - 1 : 0;
-        if (filter_match(fs, slot, vals + voff, vlen, alen == 0)) {
+        if (filter_match(fs, slot, ds.vals + voff, vlen, alen == 0)) {
             pb.mask[(v >> 6) & 3] |= 1ull << (v & 63);
             any = true;
         } else {
@@ -1425,22 +1296,18 @@ __device__ int resolve_one_filter(const uint8_t *__restrict__ payload,
         }
         voff += vlen;
     }
-    uint64_t bit0 = ((uint64_t)(p - base)) * 8;
-    uint32_t nentries = (uint32_t)rd_bits_be(base, bit0, 32);
-    uint32_t width = nentries ? (uint32_t)rd_bits_be(base, bit0 + 32, 8) : 0;
-    pb.nentries = nentries;
-    pb.width = (uint8_t)width;
-    pb.rle_bit_off = (bit0 + 40) | (in_sidecar ? TAG_SIDECAR_BIT : 0);
+    pb.nentries = ds.nentries;
+    pb.width = (uint8_t)ds.width;
+    pb.rle_bit_off = dict_rle_bit_off(ds);
     int verdict = PF_WALK;
     if (!any) {
         verdict = PF_SKIP;
-    } else if (all && count <= 256) {
+    } else if (all && ds.count <= 256) {
         pb.disabled = 1;
         verdict = PF_CLEAR;
-    } else if (nentries == 2) {
-        uint64_t code = rd_bits_be(base, bit0 + 40, width);
-        uint64_t cnt = rd_bits_be(base, bit0 + 40 + width, width);
-        if (cnt >= bd->count) {
+    } else {
+        int64_t code = dict_uniform_code(ds, bd);
+        if (code >= 0) {
             pb.uniform = 1;
             bool match = (pb.mask[(code >> 6) & 3] >> (code & 63)) & 1;
             verdict = match ? PF_CLEAR : PF_SKIP;
@@ -1450,9 +1317,12 @@ __device__ int resolve_one_filter(const uint8_t *__restrict__ payload,
     return verdict;
 }
 
-// One fused launch over blocks, the shape of k_resolve_preds: every
-// conditioned slot of a block resolves against one read of its descriptor,
-// and the combined flag byte + walk-block census come out the same way.
+// One fused launch over blocks: every conditioned slot of a block resolves
+// against one read of its descriptor and writes the combined flag byte the
+// scan's hot loop prices a non-matching block at.  Every lane stays alive
+// for the ballot of the walk-block census, which lets the heavy scan pass
+// exit immediately when every verdict is uniform (the dominant entity-tag
+// case).
 __global__ void k_resolve_filter(
     const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
     const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
@@ -1477,10 +1347,12 @@ __global__ void k_resolve_filter(
         atomicAdd(walk_count, (uint32_t)__popcll(wmask));
 }
 
-// Plain-column stage, the shape of k_resolve_plain: one wave per block, a
-// wave prefix scan over the value lengths for the payload offsets, all of
-// the slot's conditions per row (nil rows — stored length 0 — follow the
-// nil rules), one ballot word per 64 rows into the bitmap arena.
+// Plain-column stage: one wave per block evaluates all of the slot's
+// conditions on every row of the normalized stream (nil rows — stored
+// length 0 — follow the nil rules) and writes one ballot word per 64 rows
+// into the bitmap arena.  The residual-predicate pushdown the reference
+// performs row-by-row on decoded [][]byte (aggregation.go:310 over
+// column.go:410 Plain columns) becomes 64 rows per step.
 __global__ __launch_bounds__(WAVE) void k_resolve_plain_filter(
     const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
     const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
@@ -1491,47 +1363,25 @@ __global__ __launch_bounds__(WAVE) void k_resolve_plain_filter(
     for (int64_t bi = blockIdx.x; bi < n_blocks; bi += gridDim.x) {
         PredBlock pb = out[bi];
         if (!pb.plain || pb.err) continue;
-        const bydb_block_desc *bd = &blocks[bi];
-        uint64_t toff = slot == 0 ? bd->tag_off
-                                  : slot == 1 ? bd->tag2_off : bd->tag3_off;
-        const uint8_t *p = (toff & TAG_SIDECAR_BIT)
-                               ? sidecar + (toff & ~TAG_SIDECAR_BIT)
-                               : payload + toff;
-        p++;  // ENC_PLAIN
-        uint64_t n = (uint64_t)p[0] | ((uint64_t)p[1] << 8) |
-                     ((uint64_t)p[2] << 16) | ((uint64_t)p[3] << 24);
-        p += 4;
-        uint8_t wt = *p++;
-        uint32_t wbytes = wt == 0 ? 1 : wt == 1 ? 2 : wt == 2 ? 4 : 8;
-        const uint8_t *lens = p;
-        const uint8_t *vals = lens + n * wbytes;
-        if (n != (uint64_t)bd->count || n > (uint64_t)PLAIN_BM_WORDS * 64) {
+        PlainStream ps;
+        if (!plain_open(payload, sidecar, &blocks[bi], slot, &ps) ||
+            ps.n > (uint64_t)PLAIN_BM_WORDS * 64) {
             if (lane == 0) out[bi].err = 1;
             continue;
         }
-        uint32_t slot_id = 0;
-        if (lane == 0) slot_id = atomicAdd(ctr, 1u);
-        slot_id = (uint32_t)__shfl((int)slot_id, 0);
+        uint32_t slot_id = claim_stream_slot(ctr, lane);
         if (slot_id >= bm_cap_streams) {
             if (lane == 0) out[bi].err = 1;   // arena exhausted: loud
             continue;
         }
         uint64_t w0 = (uint64_t)slot_id * PLAIN_BM_WORDS;
-        uint64_t carry = 0;  // payload bytes consumed by prior chunks
-        for (uint64_t base = 0; base < n; base += WAVE) {
-            uint64_t row = base + (uint64_t)lane;
-            uint64_t lp1 = 0;
-            if (row < n)
-                for (uint32_t b = 0; b < wbytes; b++)
-                    lp1 = (lp1 << 8) | lens[row * wbytes + b];
-            uint64_t vlen = lp1 ? lp1 - 1 : 0;
-            uint64_t incl = wave_incl_scan(vlen, lane);
-            uint64_t myoff = carry + incl - vlen;
-            bool match = row < n &&
-                         filter_match(fs, slot, vals + myoff, vlen, lp1 == 0);
+        uint64_t carry = 0;
+        for (uint64_t base = 0; base < ps.n; base += WAVE) {
+            PlainRow r = plain_chunk(ps, base, lane, &carry);
+            bool match = r.valid && filter_match(fs, slot, ps.vals + r.off,
+                                                 r.vlen, r.lp1 == 0);
             uint64_t word = __ballot(match);
             if (lane == 0) bm[w0 + (base >> 6)] = word;
-            carry += readlane64(incl, WAVE - 1);
         }
         if (lane == 0) out[bi].rle_bit_off = w0;
     }
@@ -3370,15 +3220,13 @@ struct bydb_session {
     uint32_t *d_dom_gids[3] = {};
     uint32_t dom_table_size[3] = {};
     uint32_t dom_n[3] = {};
-    uint8_t *d_pred_bytes = nullptr;
-    uint64_t pred_bytes_cap = 0;
-    // tag filter operators: literals + IN-set tables of the last
-    // bydb_consume_filter, and the host staging copy they upload from
+    // tag conditions: literals + IN-set tables of the last consume, and
+    // the host staging copy they upload from
     uint8_t *d_filter = nullptr;
     uint64_t filter_cap = 0;
     std::vector<uint8_t> filter_stage;
     // plain (non-dictionary) tag columns: host-normalized sidecar arena +
-    // per-row match bitmaps filled by k_resolve_plain
+    // per-row match bitmaps filled by k_resolve_plain_filter
     uint8_t *d_sidecar = nullptr;
     uint64_t sidecar_len = 0, sidecar_cap = 0;
     uint64_t n_plain_host = 0;  // (block,slot) plain streams normalized
@@ -3439,7 +3287,6 @@ extern "C" void bydb_session_destroy(bydb_session *s) {
     if (s->d_blocks) (void)hipFree(s->d_blocks);
     if (s->d_partials) (void)hipFree(s->d_partials);
     if (s->d_preds) (void)hipFree(s->d_preds);
-    if (s->d_pred_bytes) (void)hipFree(s->d_pred_bytes);
     if (s->d_filter) (void)hipFree(s->d_filter);
     if (s->d_segs) (void)hipFree(s->d_segs);
     if (s->d_groups) (void)hipFree(s->d_groups);
@@ -3765,9 +3612,6 @@ extern "C" int bydb_reset(bydb_session *s) {
     return BYDB_OK;
 }
 
-static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
-                       PredBlock *preds, int n_preds);
-
 // PredBlock / flag-byte / walk-census buffers for the resolve prepasses
 static int ensure_pred_buffers(bydb_session *s) {
     if (s->preds_cap < s->n_blocks * 3) {
@@ -3786,79 +3630,6 @@ static int ensure_pred_buffers(bydb_session *s) {
     HIP_TRY(s, hipMemsetAsync(s->d_walk_count, 0, sizeof(uint32_t),
                               s->stream));
     return BYDB_OK;
-}
-
-extern "C" int bydb_consume_multi(bydb_session *s, int64_t min_ts,
-                                  int64_t max_ts, const uint8_t *const *preds_in,
-                                  const uint64_t *pred_lens, int n_preds) {
-    HIP_TRY(s, hipSetDevice(s->device));
-    if (!s->d_acc) { s->err = "configure first"; return BYDB_ERR_STATE; }
-    if (s->n_blocks == 0) { s->err = "no part resident"; return BYDB_ERR_STATE; }
-    if (n_preds < 0 || n_preds > 3) { s->err = "n_preds must be 0..3"; return BYDB_ERR_BAD_ARG; }
-    // drop trailing disabled slots; interior empty slots mean "no
-    // constraint on that tag"
-    while (n_preds > 0 && pred_lens[n_preds - 1] == 0) n_preds--;
-    PredBlock *preds = nullptr;
-    if (n_preds > 0) {
-        int prc = ensure_pred_buffers(s);
-        if (prc != BYDB_OK) return prc;
-        uint64_t total = 0;
-        for (int i = 0; i < n_preds; i++) total += pred_lens[i];
-        if (s->pred_bytes_cap < total) {
-            if (s->d_pred_bytes) (void)hipFree(s->d_pred_bytes);
-            HIP_TRY(s, hipMalloc(&s->d_pred_bytes, total));
-            s->pred_bytes_cap = total;
-        }
-        uint64_t off = 0;
-        uint64_t offs[3] = {0, 0, 0};
-        uint64_t lens3[3] = {0, 0, 0};
-        int rthreads = 256;
-        int rblocks = (int)((s->n_blocks + rthreads - 1) / rthreads);
-        for (int i = 0; i < n_preds; i++) {
-            if (pred_lens[i])   // disabled slots may pass a NULL pointer
-                HIP_TRY(s, hipMemcpyAsync(s->d_pred_bytes + off, preds_in[i],
-                                          pred_lens[i], hipMemcpyHostToDevice,
-                                          s->stream));
-            offs[i] = off;
-            lens3[i] = pred_lens[i];
-            off += pred_lens[i];
-        }
-        // one fused launch resolves all slots + the combined flag byte
-        hipLaunchKernelGGL(k_resolve_preds, dim3(rblocks), dim3(rthreads), 0,
-                           s->stream, s->d_payload, s->d_sidecar, s->d_blocks,
-                           s->n_blocks, s->d_pred_bytes, offs[0], lens3[0],
-                           offs[1], lens3[1], offs[2], lens3[2], n_preds,
-                           s->d_preds, s->d_pred_flags, s->d_walk_count);
-        HIP_TRY(s, hipGetLastError());
-        // plain (non-dictionary) columns present: the host counted every
-        // normalized (block,slot) stream at part_append, so the bitmap
-        // arena is sized without a device round-trip
-        if (s->n_plain_host > 0) {
-            uint64_t words = s->n_plain_host * PLAIN_BM_WORDS;
-            if (words > s->pred_bm_cap) {
-                if (s->d_pred_bm) (void)hipFree(s->d_pred_bm);
-                HIP_TRY(s, hipMalloc(&s->d_pred_bm, words * sizeof(uint64_t)));
-                s->pred_bm_cap = words;
-            }
-            HIP_TRY(s, hipMemsetAsync(s->d_plain_ctr, 0, sizeof(uint32_t),
-                                      s->stream));
-            int pgrid = (int)(s->n_blocks < 65535 ? s->n_blocks : 65535);
-            off = 0;
-            for (int i = 0; i < n_preds; i++) {
-                if (pred_lens[i] == 0) continue;
-                hipLaunchKernelGGL(k_resolve_plain, dim3(pgrid), dim3(WAVE), 0,
-                                   s->stream, s->d_payload, s->d_sidecar,
-                                   s->d_blocks, s->n_blocks,
-                                   s->d_pred_bytes + off, pred_lens[i], i,
-                                   s->d_preds + (int64_t)i * s->n_blocks,
-                                   s->d_pred_bm, s->d_plain_ctr);
-                HIP_TRY(s, hipGetLastError());
-                off += pred_lens[i];
-            }
-        }
-        preds = s->d_preds;
-    }
-    return launch_scan(s, min_ts, max_ts, preds, n_preds);
 }
 
 // The scan launch shared by every consume entry point: segment index and
@@ -4051,13 +3822,11 @@ extern "C" int bydb_consume(bydb_session *s, int64_t min_ts, int64_t max_ts,
     return bydb_consume_multi(s, min_ts, max_ts, preds, lens, 1);
 }
 
-// Scan under ANDed tag conditions (header: "tag filter operators").  The
-// host validates, sorts the conditions by slot, and uploads one arena —
-// u64 section (set value offsets, set hashes), u32 section (set slots),
-// byte section (literals and set values) — in a single copy.  IN / NOT_IN
-// lists become the open-addressing table the group-by domain uses, so the
-// device probes once per value instead of comparing n_values times.  The
-// two filter resolves then feed the unchanged scan launch.
+static int consume_conds(bydb_session *s, int64_t min_ts, int64_t max_ts,
+                         const bydb_tag_cond *conds, int n_conds);
+
+// Scan under ANDed tag conditions (header: "tag filter operators"): the
+// public entry point validates, consume_conds does the work.
 extern "C" int bydb_consume_filter(bydb_session *s, int64_t min_ts,
                                    int64_t max_ts, const bydb_tag_cond *conds,
                                    int n_conds) {
@@ -4115,6 +3884,18 @@ extern "C" int bydb_consume_filter(bydb_session *s, int64_t min_ts,
             return BYDB_ERR_BAD_ARG;
         }
     }
+    return consume_conds(s, min_ts, max_ts, conds, n_conds);
+}
+
+// The one resolve stage behind every consume entry point, over conditions
+// already validated.  The host sorts the conditions by slot and uploads one
+// arena — u64 section (set value offsets, set hashes), u32 section (set
+// slots), byte section (literals and set values) — in a single copy.  IN /
+// NOT_IN lists become the open-addressing table the group-by domain uses,
+// so the device probes once per value instead of comparing n_values times.
+// The two resolves then feed the scan launch.
+static int consume_conds(bydb_session *s, int64_t min_ts, int64_t max_ts,
+                         const bydb_tag_cond *conds, int n_conds) {
     if (n_conds == 0) return launch_scan(s, min_ts, max_ts, nullptr, 0);
 
     // conditions sorted by slot (stable), arena sections built on the host
@@ -4244,6 +4025,36 @@ extern "C" int bydb_consume_filter(bydb_session *s, int64_t min_ts,
         }
     }
     return launch_scan(s, min_ts, max_ts, s->d_preds, fs.n_slots);
+}
+
+// Equality predicates: one BYDB_OP_EQ string condition per non-empty slot.
+extern "C" int bydb_consume_multi(bydb_session *s, int64_t min_ts,
+                                  int64_t max_ts, const uint8_t *const *preds_in,
+                                  const uint64_t *pred_lens, int n_preds) {
+    HIP_TRY(s, hipSetDevice(s->device));
+    if (!s->d_acc) { s->err = "configure first"; return BYDB_ERR_STATE; }
+    if (s->n_blocks == 0) { s->err = "no part resident"; return BYDB_ERR_STATE; }
+    if (n_preds < 0 || n_preds > 3) { s->err = "n_preds must be 0..3"; return BYDB_ERR_BAD_ARG; }
+    // drop trailing disabled slots; interior empty slots mean "no
+    // constraint on that tag" and may pass a NULL pointer
+    while (n_preds > 0 && pred_lens[n_preds - 1] == 0) n_preds--;
+    bydb_tag_cond conds[3];
+    uint64_t offs[3][2];
+    int n_conds = 0;
+    for (int i = 0; i < n_preds; i++) {
+        if (pred_lens[i] == 0) continue;
+        offs[n_conds][0] = 0;
+        offs[n_conds][1] = pred_lens[i];
+        bydb_tag_cond *c = &conds[n_conds];
+        c->slot = i;
+        c->op = BYDB_OP_EQ;
+        c->tag_type = BYDB_TAG_STRING;
+        c->n_values = 1;
+        c->values = preds_in[i];
+        c->value_offs = offs[n_conds];
+        n_conds++;
+    }
+    return consume_conds(s, min_ts, max_ts, conds, n_conds);
 }
 
 extern "C" double bydb_last_consume_ms(bydb_session *s) { return s->last_ms; }

@@ -164,13 +164,18 @@ int bydb_set_partials_buffer(bydb_session *s, void *dev_ptr, uint64_t len);
 /* ---- consume (BreakerOperator.Consume over the resident part) ----
  * min_ts/max_ts: inclusive row clamp (timestamp.FindRange,
  * pkg/timestamp/range.go:143-170).  pred: optional tag-equality predicate
- * value bytes (dictionary tags only), pred_len 0 = none.  Asynchronous:
- * returns after launch; bydb_finalize syncs. */
+ * value bytes on tag slot 0 (dictionary or plain column), pred_len 0 =
+ * none.  The EQ-only form of bydb_consume_filter below: one BYDB_OP_EQ
+ * string condition.  Asynchronous: returns after launch; bydb_finalize
+ * syncs. */
 int bydb_consume(bydb_session *s, int64_t min_ts, int64_t max_ts,
                  const uint8_t *pred, uint64_t pred_len);
 
 /* Conjunctive multi-tag predicate (<=3 values; preds[i] applies to the
- * block's tag slot i).  pred_lens[i] == 0 disables slot i. */
+ * block's tag slot i).  pred_lens[i] == 0 disables slot i (preds[i] may
+ * then be NULL).  The EQ-only form of bydb_consume_filter below: one
+ * BYDB_OP_EQ string condition per enabled slot, resolved by the same
+ * stage.  BYDB_ERR_BAD_ARG when n_preds is outside 0..3. */
 int bydb_consume_multi(bydb_session *s, int64_t min_ts, int64_t max_ts,
                        const uint8_t *const *preds, const uint64_t *pred_lens,
                        int n_preds);

@@ -72,7 +72,7 @@ def test_filter_parity(name, make, expect):
         assert g.count == scen.n_rows
 
 
-# ---- EQ cross-check against the old path and the oracle ----
+# ---- EQ cross-check: equality wrapper, filter entry point, oracle ----
 # (builders copied from test_gpu_predicate.py)
 def entity_tag_part(rng, n_series=8, n=3000):
     """Entity tag: constant per series (the uniform fast path)."""
@@ -103,7 +103,9 @@ def rowvary_tag_part(rng, n_series=8, n=2000):
 
 @pytest.mark.parametrize("part", [entity_tag_part, rowvary_tag_part],
                          ids=["entity", "rowvarying"])
-def test_eq_equals_old_consume_and_oracle(part):
+def test_eq_wrapper_equals_filter_and_oracle(part):
+    """consume(preds=...) builds the same EQ conditions consume_filter takes;
+    both entry points must agree with each other and with the oracle."""
     b = part(random.Random(2101))
     s = Session(0)
     s.upload_part(b)
@@ -113,11 +115,11 @@ def test_eq_equals_old_consume_and_oracle(part):
         orc = oracle_scan(b, VT_INT64, pred=pred)[0]
         s.reset()
         s.consume(preds=[pred])
-        old = s.finalize()[0]
+        wrapped = s.finalize()[0]
         s.reset()
         s.consume_filter([TagCond(0, OP_EQ, [pred])])
         new = s.finalize()[0]
-        for g in (old, new):
+        for g in (wrapped, new):
             assert (g.count, g.sum_i) == (orc.count, orc.sum_i), pred
             if orc.count:
                 assert (g.min_i, g.max_i) == (orc.min_i, orc.max_i), pred

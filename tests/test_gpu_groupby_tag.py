@@ -299,3 +299,55 @@ def test_composite_groups_with_predicate_and_clamp():
     for g, oc in zip(gs, orc):
         assert g.count == oc.count
         assert g.sum_i == oc.sum_i
+
+
+def test_empty_mask_block_skipped_under_grouping():
+    """A predicate value that a block's dictionary does not hold gives an
+    empty code mask: the block is skipped, not walked, so it contributes no
+    group key — a group living only in such blocks keeps count 0 and the
+    never-seen first-seen sentinel, as the reference's first-seen rule
+    requires for a key with no surviving row."""
+    rng = random.Random(65)
+    n = 300
+    ts = [T0 + i * MS for i in range(n)]
+    b = PartBuilder()
+    for sid in range(4):
+        late = sid >= 2
+        b.add_block_i64(sid + 1, ts, [1] * n,
+                        [rng.randint(-10**9, 10**9) for _ in range(n)])
+        # slot 0 (grouped): "qa" occurs only in blocks 2 and 3
+        envs = ENVS if late else ENVS[:3]
+        tags = [envs[rng.randrange(len(envs))] for _ in range(n)]
+        if late:
+            tags[7] = b"qa"
+        b.set_block_tag(tags)
+        # slot 1 (predicated): blocks 2 and 3 never contain r2
+        regions = [b"r0", b"r1", b"r3"] if late else \
+            [b"r0", b"r1", b"r2", b"r3"]
+        tags2 = [regions[rng.randrange(len(regions))] for _ in range(n)]
+        if not late:
+            tags2[11] = b"r2"
+        b.set_block_tag(tags2)
+    preds = [b"", b"r2"]
+    payload, blocks = oracle_blocks(b)
+    orc = o.scan_agg_bytags(payload, blocks, VT_INT64, [0], [ENVS],
+                            preds=preds)
+    s = Session(0)
+    s.upload_part(b)
+    s.configure_by_tag(VT_INT64, [AGG_SUM, AGG_COUNT, AGG_MIN, AGG_MAX], 0,
+                       ENVS)
+    s.consume(preds=preds)
+    first_seen = s.group_first_seen()
+    gs = s.finalize()
+    s.close()
+    assert sum(oc.count for oc in orc) > 0
+    for g, oc in zip(gs, orc):
+        assert g.count == oc.count
+        assert g.sum_i == oc.sum_i
+        if oc.count:
+            assert g.min_i == oc.min_i and g.max_i == oc.max_i
+    qa = ENVS.index(b"qa")
+    assert gs[qa].count == orc[qa].count == 0
+    assert first_seen[qa] == (1 << 64) - 1
+    assert all(first_seen[g] != (1 << 64) - 1
+               for g, oc in enumerate(orc) if oc.count)

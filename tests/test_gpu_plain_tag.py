@@ -2,8 +2,8 @@
 columns.  The >256-distinct dictionary bail
 (column.go:266-278, dictionary.go:58) stores a zstd'd bytes block; the
 host normalizes it at part registration (where the reference decompresses,
-zstd.go:49) and k_resolve_plain evaluates the per-row equality into a
-match bitmap consumed by the fold walkers."""
+zstd.go:49) and k_resolve_plain_filter evaluates the per-row equality into
+a match bitmap consumed by the fold walkers."""
 import random
 
 import pytest
@@ -164,3 +164,63 @@ def test_plain_groupby_partial_domain():
     assert sum(oc.count for oc in orc) > 0
     for g, oc in zip(gs, orc):
         assert (g.count, g.sum_i) == (oc.count, oc.sum_i)
+
+
+def test_small_plain_blocks_and_dict_blocks_same_slot():
+    """Equality over one slot that is plain in some blocks and a dictionary
+    in others, with plain blocks at the 64-row chunk edges of the row walk:
+    65 rows (one full chunk plus a 1-row tail) and 64 rows (exactly one
+    chunk).  The encoder only bails to plain past 256 distinct values, so
+    the two plain columns are written by hand in the reference layout
+    ([ENC_PLAIN][bytes block]) behind the builder's payload."""
+    import ctypes as C
+    import oracle as o
+    from banyandb_amd import lib
+    rng = random.Random(78)
+    pred = b"user_003"
+    sizes = [65, 64, 100, 130]
+    b = PartBuilder()
+    for sid, n in enumerate(sizes):
+        ts = [T0 + i * MS for i in range(n)]
+        b.add_block_i64(sid + 1, ts, [1] * n,
+                        [rng.randint(-10**6, 10**6) for _ in range(n)])
+        if sid == 2:      # dictionary, row-varying
+            b.set_block_tag([b"user_%03d" % rng.randrange(5) for _ in range(n)])
+        elif sid == 3:    # dictionary, uniform match
+            b.set_block_tag([pred] * n)
+    plain_cols = []
+    for n in sizes[:2]:   # values of varying length, nils, hits at the edges
+        col = [None if rng.random() < 0.1 else
+               b"user_%03d" % rng.randrange(5) + b"x" * rng.randrange(4)
+               for _ in range(n)]
+        col[0] = col[63] = col[n - 1] = pred
+        plain_cols.append(col)
+    payload = bytearray(b.payload)
+    built = b.blocks()
+    descs = (type(built[0]) * len(built))(*built)
+    for i, col in enumerate(plain_cols):
+        stream = bytes([9]) + o.bytes_block_encode(col)       # ENC_PLAIN
+        descs[i].tag_off, descs[i].tag_len = len(payload), len(stream)
+        payload.extend(stream)
+
+    class Part:           # what helpers.oracle_blocks reads of a builder
+        pass
+    part = Part()
+    part.payload = bytes(payload)
+    part.blocks = lambda: list(descs)
+    orc = oracle_scan(part, VT_INT64, pred=pred)[0]
+    want = sum(v == pred for col in plain_cols for v in col)
+    assert orc.count > want + sizes[3] and want >= 5
+
+    L = lib()
+    s = Session(0)
+    buf = (C.c_uint8 * len(payload)).from_buffer(payload)
+    s._ck(L.bydb_part_reserve(s._h, len(payload), len(descs)))
+    s._ck(L.bydb_part_append(s._h, buf, len(payload), descs, len(descs)))
+    s.configure(VT_INT64, [AGG_SUM, AGG_COUNT, AGG_MIN, AGG_MAX])
+    s.consume(pred=pred)
+    g = s.finalize()[0]
+    s.close()
+    assert g.count == orc.count
+    assert g.sum_i == orc.sum_i
+    assert g.min_i == orc.min_i and g.max_i == orc.max_i

@@ -222,3 +222,58 @@ def test_predicate_with_time_clamp():
     assert g.count == orc.count
     assert g.sum_i == orc.sum_i
     assert g.min_i == orc.min_i and g.max_i == orc.max_i
+
+
+def test_consume_multi_argument_contract():
+    """bydb_consume_multi through raw ctypes: n_preds outside 0..3 is
+    BYDB_ERR_BAD_ARG and leaves the session usable; empty slots (interior
+    or trailing) may pass a NULL pointer and mean "no constraint"; an
+    all-empty call is an unfiltered scan."""
+    import ctypes as C
+    from banyandb_amd import lib
+    L = lib()
+    u8p = C.POINTER(C.c_uint8)
+    rng = random.Random(37)
+    b = PartBuilder()
+    n = 32                                       # 2 blocks, 64 rows in all
+    ts = [T0 + i * MS for i in range(n)]
+    for sid in range(2):
+        b.add_block_i64(sid + 1, ts, [1] * n,
+                        [rng.randint(-10**9, 10**9) for _ in range(n)])
+        b.set_block_tag([ENVS[sid]] * n)                     # slot 0: entity
+        b.set_block_tag([b"r2" if (i // 5 + sid) % 2 else b"r1"
+                         for i in range(n)])                 # slot 1: runs
+
+    def multi(s, preds, n_preds):
+        """None entries pass a NULL pointer and length 0"""
+        bufs = [(C.c_uint8 * len(p)).from_buffer_copy(p) for p in preds if p]
+        it = iter(bufs)
+        arr = (u8p * 4)(*[C.cast(next(it), u8p) if p else u8p()
+                          for p in preds])
+        lens = (C.c_uint64 * 4)(*[len(p or b"") for p in preds])
+        return L.bydb_consume_multi(s._h, o.INT64_MIN, o.INT64_MAX, arr,
+                                    lens, n_preds)
+
+    def check(g, orc):
+        assert orc.count > 0
+        assert (g.count, g.sum_i) == (orc.count, orc.sum_i)
+        assert (g.min_i, g.max_i) == (orc.min_i, orc.max_i)
+
+    s = Session(0)
+    s.upload_part(b)
+    s.configure(VT_INT64, [AGG_SUM, AGG_COUNT, AGG_MIN, AGG_MAX])
+    for bad in (4, -1):
+        assert multi(s, [b"prod", b"r2", b"x", b"y"], bad) == -3
+        assert L.bydb_last_error(s._h) == b"n_preds must be 0..3"
+    s.consume(preds=[b"prod"])
+    check(s.finalize()[0], oracle_scan(b, VT_INT64, preds=[b"prod"])[0])
+    s.reset()
+    assert multi(s, [None, b"r2", None], 3) == 0
+    check(s.finalize()[0],
+          oracle_scan(b, VT_INT64, preds=[b"", b"r2", b""])[0])
+    s.reset()
+    assert multi(s, [None, None, None], 3) == 0
+    g = s.finalize()[0]
+    s.close()
+    check(g, oracle_scan(b, VT_INT64)[0])
+    assert g.count == 2 * n
