@@ -92,6 +92,15 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
     return ((uint64_t)hi << 32) | lo;
 }
 
+// A value every lane of the wave holds alike, moved to scalar registers:
+// what depends on it becomes scalar loads and wave-uniform branches.
+__device__ __forceinline__ uint64_t wave_uniform64(uint64_t v) {
+    uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    uint32_t hi =
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+
 // wave-wide inclusive scan of a u64 (wrapping adds)
 __device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v, int lane) {
 #define BYDB_SCAN_STEP64(C)                                                  \
@@ -255,7 +264,8 @@ __device__ __forceinline__ void dev_set_err(DevErr *e, unsigned code, uint64_t b
 // (d = (b>>1) ^ (-(b&1) as 0x00/0xff)) turns 4 bytes into 4 signed i8
 // lanes, and v_dot4_i32_i8 folds them against {1,1,1,1} / {0,1,2,3}
 // weights.  Per-lane accumulators stay in int32 for a whole block
-// (<= 128 bytes/lane * 63 * 8191 < 2^31).
+// (<= 144 bytes/lane * |d| <= 64 * byte index <= 8205 is about 7.6e7,
+// far below 2^31; see dense_region_t for the batched form).
 __device__ __forceinline__ int32_t dot4_i8(uint32_t a, uint32_t b, int32_t c) {
 #if defined(__gfx950__) || defined(__AMDGCN__)
     return __builtin_amdgcn_sdot4((int)a, (int)b, c, false);
@@ -273,94 +283,167 @@ __device__ __forceinline__ uint32_t swar_zigzag(uint32_t w) {
     return mag ^ (sgn * 0xffu);  // per-byte signed i8 delta
 }
 
+// The same decode without the quarter-rate 32-bit multiply, for the
+// dense fold: 0x80 - {0,1} = {0x80,0x7f} borrows nothing across bytes,
+// and ^ 0x80 turns that into the per-byte {0x00,0xff} sign mask.
+__device__ __forceinline__ uint32_t swar_zigzag_sub(uint32_t w) {
+    uint32_t mag = (w >> 1) & 0x7f7f7f7fu;
+    uint32_t sgn = w & 0x01010101u;
+    uint32_t neg = (0x80808080u - sgn) ^ 0x80808080u;
+    return mag ^ neg;
+}
+
+// The payload arena is device (global) memory; saying so on the pointer
+// keeps the dense loads global_load_dwordx4 even where the fold is not
+// inlined into the kernel and `stream` arrives as a generic pointer.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(1))) u32x4 *gptr_u4;
+
+// A dense chunk is 1 KiB: 16 bytes per lane, one wave load instruction.
+// A block's stream (<= 8191 bytes) plus its <= 15-byte head offset spans
+// at most DENSE_CHUNKS_BLOCK of them.
+#define DENSE_CHUNK_BYTES 1024
+#define DENSE_CHUNKS_BLOCK 9
+// The clamped closed-form instantiation carries the FindRange state next
+// to the fold: with nine chunks in flight it spills 12 bytes, with five
+// it has no scratch (108 VGPRs); a clamped block then takes two batches.
+#define DENSE_CHUNKS_CLAMP 5
+// Batch depth of the out-of-line fold that the value-scan instantiations
+// and fold_range call: two chunks keep it inside the registers a device
+// function may clobber without saving them, so those callers gain no
+// scratch (three already cost fold_range 8 bytes, four cost 28-36).
+#define DENSE_CHUNKS_CALL 2
+
+// Byte-lane keep mask of the dword at chunk-relative offset r: 0xff for
+// the bytes whose offset lies in [lo_rel, hi_rel), 0 for the rest.  A
+// zeroed byte zigzag-decodes to delta 0 and adds nothing to either sum.
+__device__ __forceinline__ uint32_t dense_keep(int32_t r, int32_t lo_rel,
+                                               int32_t hi_rel) {
+    int32_t a = lo_rel - r, b = hi_rel - r;
+    a = a < 0 ? 0 : a > 4 ? 4 : a;   // bytes dropped at the low end
+    b = b < 0 ? 0 : b > 4 ? 4 : b;   // bytes kept from the low end
+    uint32_t m_hi = (uint32_t)((1ull << (8 * b)) - 1ull);
+    uint32_t m_lo = (uint32_t)(0xffffffffull << (8 * a));
+    return m_hi & m_lo;
+}
+
+// Fold one lane's 16 bytes: T = sum of the 16 deltas, K = sum of
+// (byte offset within the 16) * delta.
+__device__ __forceinline__ void dense_fold16(u32x4 w, int32_t *T, int32_t *K) {
+    uint32_t s0 = swar_zigzag_sub(w.x), s1 = swar_zigzag_sub(w.y),
+             s2 = swar_zigzag_sub(w.z), s3 = swar_zigzag_sub(w.w);
+    *T = dot4_i8(s0, 0x01010101u, dot4_i8(s1, 0x01010101u,
+         dot4_i8(s2, 0x01010101u, dot4_i8(s3, 0x01010101u, 0))));
+    *K = dot4_i8(s0, 0x03020100u, dot4_i8(s1, 0x07060504u,
+         dot4_i8(s2, 0x0b0a0908u, dot4_i8(s3, 0x0f0e0d0cu, 0))));
+}
+
 // Fold Sum(d_j) and Sum(bidx*d_j) over stream bytes bidx in [lo, hi)
-// (delta j = bidx+1).  Interior dwords go through the dense dot4 loop;
-// the <=6 boundary bytes are folded by lane 0.
-__device__ void dense_region(const uint8_t *stream, int64_t lo, int64_t hi,
-                             int lane, int64_t *out_sum_d, int64_t *out_sum_jd) {
+// (delta j = bidx+1).  lo, hi and stream MUST be wave-uniform: they are
+// taken from the first active lane, so a caller with per-lane ranges
+// would get that lane's sums in every lane.  The region is read as
+// 1-KiB chunks of 16 bytes per lane, starting at the 16-byte boundary at
+// or below stream+lo; bytes outside [lo, hi) are zeroed in registers, so
+// only the first and the last chunk are masked and nothing is folded by
+// a single lane.  Chunks go in batches of NB, and all chunks of a batch
+// are issued before the first is folded.  With NB = DENSE_CHUNKS_BLOCK a
+// block is one batch: one memory round trip per block, and a full-length
+// block folds under counted waits while its later chunks arrive.
+// A chunk is issued only if it starts before hi (the last one only for
+// the lanes that do), so the over-read stays below one chunk past hi —
+// inside the arena's zeroed 4-KiB slack.
+// Per-lane accumulators stay in int32 for a whole batch: with NB = 9,
+// <= 144 bytes/lane * |d| <= 64 * batch-relative offset <= 9215 is about
+// 8.5e7 < 2^31; the batch base is applied in int64.
+template <int NB>
+__device__ __forceinline__ void dense_region_t(
+    const uint8_t *stream, int64_t lo, int64_t hi, int lane,
+    int64_t *out_sum_d, int64_t *out_sum_jd) {
     *out_sum_d = 0;
     *out_sum_jd = 0;
+    lo = (int64_t)wave_uniform64((uint64_t)lo);
+    hi = (int64_t)wave_uniform64((uint64_t)hi);
     if (hi <= lo) return;
-    // aligned interior: first dword-aligned byte >= lo, last < hi
-    uintptr_t s0 = (uintptr_t)stream;
-    int64_t alo = (int64_t)(((s0 + (uint64_t)lo + 3) & ~(uintptr_t)3) - s0);
-    int64_t ahi = (int64_t)(((s0 + (uint64_t)hi) & ~(uintptr_t)3) - s0);
-    int32_t acc_d = 0;
-    int64_t acc_jd = 0;   // 64-bit: boundary folds may exceed int32 ranges? no — keep 64 for safety on jd only at fold
-    int32_t acc_jd32 = 0;
-    if (ahi > alo) {
-        const uint32_t *p = (const uint32_t *)(s0 + (uint64_t)alo);
-        int64_t ndw = (ahi - alo) / 4;
-        int64_t q = lane;
-        // software-pipelined 4-deep batches: fold batch N while batch
-        // N+1's four loads are in flight (the plain 4-deep loop leaves
-        // the wave parked on its own loads ~79% of cycles)
-        if (q + 192 < ndw) {
-            uint32_t w0 = p[q], w1 = p[q + 64], w2 = p[q + 128],
-                     w3 = p[q + 192];
-            for (;;) {
-                int64_t qn = q + 256;
-                bool more = qn + 192 < ndw;
-                uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
-                if (more) {
-                    n0 = p[qn];
-                    n1 = p[qn + 64];
-                    n2 = p[qn + 128];
-                    n3 = p[qn + 192];
-                }
-                int32_t b0 = (int32_t)(alo + 4 * q);
-                uint32_t s_0 = swar_zigzag(w0), s_1 = swar_zigzag(w1),
-                         s_2 = swar_zigzag(w2), s_3 = swar_zigzag(w3);
-                int32_t t0 = dot4_i8(s_0, 0x01010101u, 0);
-                int32_t t1 = dot4_i8(s_1, 0x01010101u, 0);
-                int32_t t2 = dot4_i8(s_2, 0x01010101u, 0);
-                int32_t t3 = dot4_i8(s_3, 0x01010101u, 0);
-                acc_d += t0 + t1 + t2 + t3;
-                acc_jd32 += dot4_i8(s_0, 0x03020100u, 0) +
-                            dot4_i8(s_1, 0x03020100u, 0) +
-                            dot4_i8(s_2, 0x03020100u, 0) +
-                            dot4_i8(s_3, 0x03020100u, 0);
-                acc_jd32 += b0 * t0 + (b0 + 256) * t1 + (b0 + 512) * t2 +
-                            (b0 + 768) * t3;
-                q = qn;
-                if (!more) break;
-                w0 = n0;
-                w1 = n1;
-                w2 = n2;
-                w3 = n3;
+    // the integer value of the pointer serves the alignment only
+    const uint32_t mis = (uint32_t)__builtin_amdgcn_readfirstlane(
+                             (int)((uint32_t)(uintptr_t)stream + (uint32_t)lo)) & 15u;
+    int64_t a0 = lo - (int64_t)mis;
+    int64_t sum_d = 0, sum_jd = 0;
+    const int32_t lane_off = lane * 16;
+    do {
+        const gptr_u4 p = (gptr_u4)(stream + a0) + lane;
+        const int64_t span = hi - a0;
+        const int32_t hi_rel = span > NB * DENSE_CHUNK_BYTES
+                                   ? NB * DENSE_CHUNK_BYTES
+                                   : (int32_t)span;
+        const int32_t lo_rel = lo > a0 ? (int32_t)(lo - a0) : 0;
+        const int nch = (hi_rel + DENSE_CHUNK_BYTES - 1) / DENSE_CHUNK_BYTES;
+        int32_t acc_d = 0, acc_c = 0, acc_k = 0;
+        auto fold = [&](int c, u32x4 v, bool may_mask) {
+            if (may_mask && ((c == 0 && lo_rel > 0) ||
+                             (c + 1) * DENSE_CHUNK_BYTES > hi_rel)) {
+                int32_t r = c * DENSE_CHUNK_BYTES + lane_off;
+                v.x &= dense_keep(r, lo_rel, hi_rel);
+                v.y &= dense_keep(r + 4, lo_rel, hi_rel);
+                v.z &= dense_keep(r + 8, lo_rel, hi_rel);
+                v.w &= dense_keep(r + 12, lo_rel, hi_rel);
             }
+            int32_t T, K;
+            dense_fold16(v, &T, &K);
+            acc_d += T;
+            acc_c += __mul24(c, T);   // |T| <= 16 * 64: full-rate 24-bit mad
+            acc_k += K;
+        };
+        u32x4 w[NB];
+        if (nch >= NB - 1) {
+            // full batch: NB-1 unconditional loads back to back, the last
+            // chunk only for the lanes that still start before hi; only
+            // chunk 0 (head) and chunk NB-2 (tail) can need a mask here,
+            // chunk NB-1 is folded below and always takes the tail mask
+#pragma unroll
+            for (int c = 0; c < NB - 1; c++) w[c] = p[c * 64];
+            w[NB - 1] = u32x4{0, 0, 0, 0};
+            if ((NB - 1) * DENSE_CHUNK_BYTES + lane_off < hi_rel)
+                w[NB - 1] = p[(NB - 1) * 64];
+#pragma unroll
+            for (int c = 0; c < NB - 1; c++) {
+                fold(c, w[c], c == 0 || c == NB - 2);
+                // Keep the folds in issue order.  Left alone, the folds
+                // sink below the tail-mask branch and the scheduler
+                // starts with a late chunk, so the first wait covers most
+                // of the batch.  The empty statement pins the running
+                // sums after chunk c; the barrier stops the scheduler
+                // from moving a later chunk's math above it.
+                asm volatile("" : "+v"(acc_d), "+v"(acc_c), "+v"(acc_k));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (nch > NB - 1) fold(NB - 1, w[NB - 1], true);
+        } else {
+            // short region: issue only the chunks (and lanes) that start
+            // before hi, then fold them after a single wait
+#pragma unroll
+            for (int c = 0; c < NB - 2; c++) {
+                w[c] = u32x4{0, 0, 0, 0};
+                if (c * DENSE_CHUNK_BYTES + lane_off < hi_rel)
+                    w[c] = p[c * 64];
+            }
+#pragma unroll
+            for (int c = 0; c < NB - 2; c++)
+                if (nch > c) fold(c, w[c], true);
         }
-        for (; q < ndw; q += 64) {
-            uint32_t w0 = p[q];
-            uint32_t s_0 = swar_zigzag(w0);
-            int32_t t0 = dot4_i8(s_0, 0x01010101u, 0);
-            int32_t k0 = dot4_i8(s_0, 0x03020100u, 0);
-            acc_d += t0;
-            acc_jd32 += k0 + (int32_t)(alo + 4 * q) * t0;
-        }
-    }
-    acc_jd += acc_jd32;
-    // boundary bytes on lane 0: with an interior, the head [lo, alo) and
-    // tail [ahi, hi); without one, the whole [lo, hi)
-    if (lane == 0) {
-        int64_t h_lo = lo, h_hi, t_lo, t_hi;
-        if (ahi > alo) { h_hi = alo; t_lo = ahi; t_hi = hi; }
-        else { h_hi = hi; t_lo = 0; t_hi = 0; }
-        for (int64_t b = h_lo; b < h_hi; b++) {
-            uint32_t c = stream[b];
-            int32_t d = (int32_t)(c >> 1) ^ -(int32_t)(c & 1);
-            acc_d += d;
-            acc_jd += (int64_t)b * d;
-        }
-        for (int64_t b = t_lo; b < t_hi; b++) {
-            uint32_t c = stream[b];
-            int32_t d = (int32_t)(c >> 1) ^ -(int32_t)(c & 1);
-            acc_d += d;
-            acc_jd += (int64_t)b * d;
-        }
-    }
-    *out_sum_d = (int64_t)acc_d;
-    *out_sum_jd = acc_jd;
+        int32_t rel = lane_off * acc_d + DENSE_CHUNK_BYTES * acc_c + acc_k;
+        sum_d += (int64_t)acc_d;
+        sum_jd += a0 * (int64_t)acc_d + (int64_t)rel;
+        a0 += NB * DENSE_CHUNK_BYTES;
+    } while (a0 < hi);
+    *out_sum_d = sum_d;
+    *out_sum_jd = sum_jd;
+}
+
+__device__ void dense_region(const uint8_t *stream, int64_t lo, int64_t hi,
+                             int lane, int64_t *out_sum_d, int64_t *out_sum_jd) {
+    dense_region_t<DENSE_CHUNKS_CALL>(stream, lo, hi, lane, out_sum_d,
+                                      out_sum_jd);
 }
 
 // wave-wide inclusive scan of an int32 (per-window lane sums)
@@ -445,21 +528,30 @@ __device__ void dense_minmax(const uint8_t *stream, int64_t b_lo, int64_t b_hi,
 //   region1 bytes [0, min(r0,jend)):          contributes nsel * S1d
 //   region2 bytes [min(r0,jend), jend):       contributes (r1+1)*S2d - S2jd'
 // where S2jd' uses delta index j = bidx+1.
-__device__ uint64_t dense_delta_weighted(const uint8_t *stream,
-                                         int64_t n_deltas, int64_t r0,
-                                         int64_t r1, int lane) {
+template <int NB>
+__device__ __forceinline__ uint64_t dense_delta_weighted_t(
+    const uint8_t *stream, int64_t n_deltas, int64_t r0, int64_t r1,
+    int lane) {
     int64_t jend = r1 < n_deltas ? r1 : n_deltas;
     if (jend < 1) return 0;
     uint64_t nsel = (uint64_t)(r1 - r0 + 1);
     int64_t b1 = r0 < jend ? r0 : jend;  // deltas 1..b1 have weight nsel
-    int64_t s1d, s1jd, s2d, s2jd;
-    dense_region(stream, 0, b1, lane, &s1d, &s1jd);
-    dense_region(stream, b1, jend, lane, &s2d, &s2jd);
+    int64_t s1d = 0, s1jd = 0, s2d, s2jd;
+    // whole-range queries have r0 == 0: no constant-weight region to read
+    if (b1 > 0) dense_region_t<NB>(stream, 0, b1, lane, &s1d, &s1jd);
+    dense_region_t<NB>(stream, b1, jend, lane, &s2d, &s2jd);
     // j = bidx + 1  =>  sum j*d = sum bidx*d + sum d
     uint64_t sum_jd2 = (uint64_t)s2jd + (uint64_t)s2d;
     uint64_t acc = nsel * (uint64_t)s1d;
     acc += (uint64_t)(r1 + 1) * (uint64_t)s2d - sum_jd2;
     return acc;
+}
+
+__device__ uint64_t dense_delta_weighted(const uint8_t *stream,
+                                         int64_t n_deltas, int64_t r0,
+                                         int64_t r1, int lane) {
+    return dense_delta_weighted_t<DENSE_CHUNKS_CALL>(stream, n_deltas, r0, r1,
+                                                     lane);
 }
 
 // Fast weighted delta fold: 256-byte windows (one dword per lane) with an
@@ -485,9 +577,10 @@ __device__ uint64_t fold_delta_weighted_fast(const uint8_t *stream,
     uint64_t nsel = (uint64_t)(r1 - r0 + 1);
     // 256-byte windows at 4-byte-aligned absolute addresses; `off` is the
     // unconsumed-prefix length (bytes before the next value start).
-    const uint32_t *wp =
-        (const uint32_t *)((uintptr_t)(stream + pos) & ~(uintptr_t)3);
-    unsigned off = (unsigned)((uintptr_t)(stream + pos) - (uintptr_t)wp);
+    // (aligned down by pointer arithmetic, not through an integer, so the
+    // window loads stay in the global address space)
+    unsigned off = (unsigned)((uintptr_t)(stream + pos) & 3);
+    const uint32_t *wp = (const uint32_t *)(stream + pos - off);
     uint32_t w = wp[lane];
     while (j <= jend) {
         uint32_t w_next = wp[64 + lane];               // prefetch next window
@@ -556,8 +649,8 @@ __device__ uint64_t fold_delta_weighted_fast(const uint8_t *stream,
                 if (j + nterm2 > jend) { j = jend + 1; break; }
                 j += nterm2;
                 pos += (uint64_t)(ll2 + 1);
-                wp = (const uint32_t *)((uintptr_t)(stream + pos) & ~(uintptr_t)3);
-                off = (unsigned)((uintptr_t)(stream + pos) - (uintptr_t)wp);
+                off = (unsigned)((uintptr_t)(stream + pos) & 3);
+                wp = (const uint32_t *)(stream + pos - off);
                 w = wp[lane];
                 continue;
             }
@@ -586,8 +679,8 @@ __device__ uint64_t fold_delta_weighted_fast(const uint8_t *stream,
             if (j + nterm > jend) { j = jend + 1; break; }
             j += nterm;
             pos += (uint64_t)(64 - __clzll(emask));
-            wp = (const uint32_t *)((uintptr_t)(stream + pos) & ~(uintptr_t)3);
-            off = (unsigned)((uintptr_t)(stream + pos) - (uintptr_t)wp);
+            off = (unsigned)((uintptr_t)(stream + pos) & 3);
+            wp = (const uint32_t *)(stream + pos - off);
             w = wp[lane];
         }
     }
@@ -2385,17 +2478,25 @@ __device__ void fold_range(const uint8_t *fstream, uint8_t fenc, int64_t first,
 template <bool EN_VALUES, bool EN_PREDS, bool EN_GROUPS, bool EN_WALK,
           bool EN_CLAMP>
 // Occupancy: 4 waves/SIMD for the value-scan instantiations — requesting
-// 6 forces scratch spills into the window loop and measured ~1.6x SLOWER;
-// the closed-form-only instantiation fits 6 without spills.
+// 6 forces scratch spills into the window loop and measured ~1.6x SLOWER.
 // Occupancy: the clamp-free value-scan instantiations (the analytic
 // full-range f64/min-max path) run at EIGHT waves/SIMD — swept 4..8 on
 // hardware twice: 7 won before the compile-time full-range flag
 // (6.40 -> 5.67 ms on configs[2]), 8 wins after it shed the selection
 // branch's registers (-> ~5.25 ms); the extra waves hide the decode's
 // dependency bubbles and the VGPR-spill cost stays below the win.  The
-// other instantiations keep 4 (more state: clamp / groups), the
-// closed-form-only ones 6 (8 measured WORSE there: 2.84 -> 3.25 ms).
-__global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (EN_VALUES || EN_PREDS || EN_GROUPS) ? 4 : 6) void k_scan_agg_t(
+// other instantiations keep 4 (more state: clamp / groups).  So do the
+// closed-form-only ones since the dense fold keeps a whole block (nine
+// 16-byte loads per lane) in flight per wave: 16 waves/CU already hold
+// ~144 KiB in flight, and 128 VGPRs leave the full-range one with no
+// scratch.  Swept on hardware, headline kernel ms, two runs each:
+// 4 waves 1.90/1.97, 6 waves 2.27/2.27 (32 B scratch), 8 waves 3.73/3.76
+// (256 B scratch) — profiles/dense_wide_loads.txt.
+// The predicate light pass without clamp (<0,1,0,0,0>) asks for 5: it
+// skips most blocks on a flag byte and is bound by per-item latency; at
+// 100 VGPRs / 4 waves it measured 15% slower than at 95 / 5 on the
+// group4096_pred3 and mixed workloads.
+__global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (!EN_VALUES && EN_PREDS && !EN_GROUPS && !EN_WALK && !EN_CLAMP) ? 5 : 4) void k_scan_agg_t(
     const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
     const bydb_block_desc *__restrict__ blocks,
     int64_t n_blocks, int64_t min_ts, int64_t max_ts, int flags,
@@ -2419,7 +2520,21 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
     const SegEntry *segs = EN_VALUES ? segs_in : nullptr;
     const GroupBlock *groups = EN_GROUPS ? groups_in : nullptr;
     const int lane = threadIdx.x & 63;
-    const int wave_in_block = threadIdx.x >> 6;
+    // In the closed-form instantiations (no value reconstruction, tag
+    // predicates or tag group-by) the per-item preamble is wave-uniform:
+    // the wave index goes through readfirstlane, so the item index and the
+    // descriptor live in scalar registers and the descriptor is fetched by
+    // scalar loads (descriptors are written by host copies before the
+    // launch, so the read-only scalar cache is safe for them).
+    // Not with EN_GROUPS: the run-merge state leaves no scalar registers
+    // for two descriptors, and what spills there lands in scratch.  Not
+    // with EN_PREDS: a skipped block costs one flag byte there, and
+    // fetching every descriptor ahead measured 5% slower on the mixed
+    // workload (profiles/dense_wide_loads.txt).
+    constexpr bool UNI_DESC = !EN_VALUES && !EN_PREDS && !EN_GROUPS;
+    const int wave_in_block =
+        UNI_DESC ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))
+                 : (int)(threadIdx.x >> 6);
     int64_t wave_id = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave_in_block;
     int64_t n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
 
@@ -2435,13 +2550,26 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
     // Strided assignment (not contiguous ranges): predicates skip blocks
     // in long runs, and contiguous ranges turn those runs into idle waves.
     const int64_t n_items = segs ? n_blocks * MAX_SEGS : n_blocks;
+    // UNI_DESC: the descriptor of the item after this one is requested at
+    // the top of each iteration and consumed only when the loop advances,
+    // so its latency hides behind the current block's fold; an item pays
+    // no descriptor round trip after the wave's first.
+    // (Both stay unused, and vanish, in the other instantiations.)
+    bydb_block_desc d_cur = {}, d_nxt = {};
+    if (UNI_DESC && wave_id < n_items) d_nxt = blocks[wave_id];
     for (int64_t wi = wave_id; wi < n_items; wi += n_waves) {
         const int64_t bi = segs ? wi / MAX_SEGS : wi;
         const int seg = segs ? (int)(wi % MAX_SEGS) : 0;
-        // per-item cold-start: issue the independent scalar loads
-        // (descriptor, predicate flag, segment entries) back-to-back so
-        // the item pays ONE memory latency, not a chain of them
-        const bydb_block_desc *bd = &blocks[bi];
+        if (UNI_DESC) {
+            d_cur = d_nxt;   // requested one iteration ago
+            // clamped to the last item, so the request is unconditional
+            int64_t nx = wi + n_waves < n_items ? wi + n_waves : n_items - 1;
+            d_nxt = blocks[nx];
+        }
+        // otherwise: issue the independent per-lane loads (descriptor,
+        // predicate flag, segment entries) back-to-back ahead of their
+        // first use
+        const bydb_block_desc *bd = UNI_DESC ? &d_cur : &blocks[bi];
         const uint8_t pf_pre =
             (EN_PREDS && preds != nullptr) ? pred_flags[bi] : PF_CLEAR;
         uint32_t seg0_off = SEG_INELIGIBLE;
@@ -2899,9 +3027,13 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
                 if (!dod) {
                     if (bd->field_len == (uint64_t)(n - 1)) {
                         // stream length == delta count -> every varint is
-                        // one byte: dense dot4 fold
-                        acc = dense_delta_weighted(fstream, n - 1, r0, r1,
-                                                   lane);
+                        // one byte: dense dot4 fold, inlined with the whole
+                        // block in flight in the closed-form instantiations
+                        acc = !UNI_DESC
+                                  ? dense_delta_weighted(fstream, n - 1, r0,
+                                                         r1, lane)
+                                  : dense_delta_weighted_t<EN_CLAMP ? DENSE_CHUNKS_CLAMP : DENSE_CHUNKS_BLOCK>(
+                                        fstream, n - 1, r0, r1, lane);
                     } else {
                         acc = fold_delta_weighted_fast(fstream, n - 1, r0, r1,
                                                        lane, derr,
