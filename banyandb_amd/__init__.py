@@ -113,6 +113,114 @@ class TagCond:
                        for v in values]
 
 
+# criteria tree nodes (AND / OR = modelv1.LogicalExpression.LogicalOp)
+NODE_LEAF, NODE_AND, NODE_OR = 0, 1, 2
+
+
+class FilterNodeC(C.Structure):
+    # must mirror bydb_filter_node in include/bydb_gpu.h exactly
+    _fields_ = [
+        ("op", C.c_int32),
+        ("left", C.c_int32),
+        ("right", C.c_int32),
+    ]
+
+
+class TreeNode:
+    """Binary AND / OR node of a criteria tree; children are TagCond leaves
+    or TreeNodes."""
+
+    def __init__(self, op, left, right):
+        self.op = op
+        self.left = left
+        self.right = right
+
+
+def _fold_nodes(op, children):
+    if not children:
+        raise ValueError("And / Or need at least one child")
+    node = children[0]
+    for c in children[1:]:      # left fold, as isMatch merges its sub-nodes
+        node = TreeNode(op, node, c)
+    return node
+
+
+def And(*children):
+    """AND of TagCond leaves / sub-trees, folded left into binary nodes."""
+    return _fold_nodes(NODE_AND, children)
+
+
+def Or(*children):
+    """OR of TagCond leaves / sub-trees, folded left into binary nodes."""
+    return _fold_nodes(NODE_OR, children)
+
+
+def flatten_tree(tree):
+    """(conds, nodes) of a criteria tree: conditions in leaf order and
+    (op, left, right) nodes in post-order, the bydb_filter_node encoding.
+    None is the empty tree ([], [])."""
+    conds, nodes = [], []
+
+    def walk(t):
+        if isinstance(t, TagCond):
+            conds.append(t)
+            nodes.append((NODE_LEAF, len(conds) - 1, 0))
+        else:
+            left = walk(t.left)
+            right = walk(t.right)
+            nodes.append((t.op, left, right))
+        return len(nodes) - 1
+
+    if tree is not None:
+        walk(tree)
+    return conds, nodes
+
+
+def _nodes_c(nodes):
+    arr = (FilterNodeC * max(len(nodes), 1))()
+    for i, (op, left, right) in enumerate(nodes):
+        arr[i].op, arr[i].left, arr[i].right = op, left, right
+    return arr
+
+
+def _conds_c(conds):
+    """TagCondC array of TagCond objects plus the buffers it points into."""
+    arr = (TagCondC * max(len(conds), 1))()
+    keep = []
+    for i, c in enumerate(conds):
+        blob = b"".join(c.values)
+        offs = [0]
+        for v in c.values:
+            offs.append(offs[-1] + len(v))
+        buf = (C.c_uint8 * max(len(blob), 1)).from_buffer_copy(blob or b"\0")
+        oa = (C.c_uint64 * len(offs))(*offs)
+        keep.append((buf, oa))
+        arr[i].slot = c.slot
+        arr[i].op = c.op
+        arr[i].tag_type = c.tag_type
+        arr[i].n_values = len(c.values)
+        arr[i].values = C.cast(buf, C.POINTER(C.c_uint8))
+        arr[i].value_offs = oa
+    return arr, keep
+
+
+def filter_tree_table(tree):
+    """The 256-bit truth table of a criteria tree as a Python int: bit sig
+    is the tree's result when leaf i (in leaf order) evaluates to bit i of
+    sig.  Pure host; raises ValueError on a malformed tree."""
+    conds, nodes = flatten_tree(tree)
+    return filter_nodes_table(nodes, len(conds))
+
+
+def filter_nodes_table(nodes, n_conds):
+    """filter_tree_table over raw (op, left, right) nodes."""
+    out = (C.c_uint64 * 4)()
+    rc = _lib.bydb_filter_tree_table(_nodes_c(nodes), len(nodes), n_conds, out)
+    if rc != 0:
+        raise ValueError(f"bydb_filter_tree_table rc={rc}")
+    return sum(int(out[w]) << (64 * w) for w in range(4))
+
+
 def _build_if_possible():
     from banyandb_amd.build import build
     return build(verbose=False)
@@ -177,6 +285,15 @@ def _load():
     lib.bydb_consume_filter.restype = C.c_int
     lib.bydb_consume_filter.argtypes = [C.c_void_p, C.c_int64, C.c_int64,
                                         C.POINTER(TagCondC), C.c_int]
+    lib.bydb_consume_filter_tree.restype = C.c_int
+    lib.bydb_consume_filter_tree.argtypes = [C.c_void_p, C.c_int64, C.c_int64,
+                                             C.POINTER(TagCondC), C.c_int,
+                                             C.POINTER(FilterNodeC), C.c_int]
+    lib.bydb_filter_tree_table.restype = C.c_int
+    lib.bydb_filter_tree_table.argtypes = [C.POINTER(FilterNodeC), C.c_int,
+                                           C.c_int, C.POINTER(C.c_uint64)]
+    lib.bydb_filter_tree_stats.restype = C.c_int
+    lib.bydb_filter_tree_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     lib.bydb_finalize.restype = C.c_int
     lib.bydb_finalize.argtypes = [C.c_void_p, C.POINTER(Result), C.c_int64]
     lib.bydb_finalize_partials.restype = C.c_int
@@ -518,24 +635,26 @@ class Session:
     def consume_filter(self, conds, min_ts=INT64_MIN, max_ts=INT64_MAX):
         """Scan under ANDed TagCond conditions (EQ, NE, LT, LE, GT, GE, IN,
         NOT_IN); an empty list is an unfiltered scan."""
-        arr = (TagCondC * max(len(conds), 1))()
-        keep = []
-        for i, c in enumerate(conds):
-            blob = b"".join(c.values)
-            offs = [0]
-            for v in c.values:
-                offs.append(offs[-1] + len(v))
-            buf = (C.c_uint8 * max(len(blob), 1)).from_buffer_copy(blob or b"\0")
-            oa = (C.c_uint64 * len(offs))(*offs)
-            keep.append((buf, oa))
-            arr[i].slot = c.slot
-            arr[i].op = c.op
-            arr[i].tag_type = c.tag_type
-            arr[i].n_values = len(c.values)
-            arr[i].values = C.cast(buf, C.POINTER(C.c_uint8))
-            arr[i].value_offs = oa
+        arr, _keep = _conds_c(conds)
         self._ck(_lib.bydb_consume_filter(self._h, min_ts, max_ts, arr,
                                           len(conds)))
+
+    def consume_filter_tree(self, tree, min_ts=INT64_MIN, max_ts=INT64_MAX):
+        """Scan under an AND / OR criteria tree built with And(...) /
+        Or(...) over TagCond leaves (a bare TagCond is a one-leaf tree, None
+        an unfiltered scan); at most FILTER_MAX_CONDS leaves."""
+        conds, nodes = flatten_tree(tree)
+        arr, _keep = _conds_c(conds)
+        self._ck(_lib.bydb_consume_filter_tree(
+            self._h, min_ts, max_ts, arr, len(conds), _nodes_c(nodes),
+            len(nodes)))
+
+    def filter_tree_stats(self):
+        """Blocks of the last consume_filter_tree by verdict: [clear, skip,
+        code-mask walk, row-bitmap walk]; zeros when the tree had no OR."""
+        out = (C.c_uint64 * 4)()
+        self._ck(_lib.bydb_filter_tree_stats(self._h, out))
+        return [int(x) for x in out]
 
     def finalize(self):
         out = (Result * self.n_groups)()

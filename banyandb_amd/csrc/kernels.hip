@@ -1250,8 +1250,9 @@ __global__ __launch_bounds__(WAVE) void k_resolve_plain_groups(
 //       never (rangeTag.Match :465-503); string c = strings.Compare, int
 //       c = int(lit - val) with wrapping int64 subtraction
 //       (expr_literal.go:65-70, 241-246)
-// Conditions are ANDed (andLogicalNode); OR across conditions is out of
-// scope.
+// k_resolve_filter ANDs the conditions (andLogicalNode); AND / OR criteria
+// trees resolve through k_resolve_tree / k_resolve_tree_rows further down,
+// which write the same PredBlocks and flag byte.
 // Slot verdicts, and the values of the combined per-block flag byte:
 #define PF_CLEAR 0   // every row matches -> fold unpredicated
 #define PF_SKIP 1    // no row matches -> skip block
@@ -1293,40 +1294,41 @@ __device__ __forceinline__ int64_t i64_from_cell(const uint8_t *p) {
     return (int64_t)(u ^ (1ull << 63));
 }
 
-// All of one slot's conditions against one tag value (nil: v unused).
+// One condition against one tag value (nil: v unused).
+__device__ __forceinline__ bool cond_match(const FilterCond &c,
+                                           const uint8_t *v, uint64_t len,
+                                           bool nil) {
+    if (c.op == BYDB_OP_EQ || c.op == BYDB_OP_NE) {
+        bool eq = !nil && len == c.lit_len &&
+                  bytes_compare(c.lit, c.lit_len, v, len) == 0;
+        return c.op == BYDB_OP_EQ ? eq : !eq;
+    }
+    if (c.op == BYDB_OP_IN || c.op == BYDB_OP_NOT_IN) {
+        bool in = !nil && domain_lookup(&c.set, v, len) != GID_NONE;
+        return c.op == BYDB_OP_IN ? in : !in;
+    }
+    if (nil) return false;      // Compare returns ok=false
+    int cmp;                    // sign of literal.Compare(value)
+    if (c.is_int) {
+        if (len != 8) return false;
+        // Go int64 subtraction wraps: take the sign of the
+        // two's-complement difference, not of the true one
+        int64_t d = (int64_t)((uint64_t)c.lit_i - (uint64_t)i64_from_cell(v));
+        cmp = d < 0 ? -1 : d > 0 ? 1 : 0;
+    } else {
+        cmp = bytes_compare(c.lit, c.lit_len, v, len);
+    }
+    return c.op == BYDB_OP_GT   ? cmp < 0
+           : c.op == BYDB_OP_GE ? cmp <= 0
+           : c.op == BYDB_OP_LT ? cmp > 0
+                                : cmp >= 0;
+}
+
+// All of one slot's conditions against one tag value: the AND of them.
 __device__ bool filter_match(const FilterSet &fs, int slot, const uint8_t *v,
                              uint64_t len, bool nil) {
-    for (int i = fs.first[slot]; i < fs.first[slot + 1]; i++) {
-        const FilterCond &c = fs.c[i];
-        bool m;
-        if (c.op == BYDB_OP_EQ || c.op == BYDB_OP_NE) {
-            bool eq = !nil && len == c.lit_len &&
-                      bytes_compare(c.lit, c.lit_len, v, len) == 0;
-            m = c.op == BYDB_OP_EQ ? eq : !eq;
-        } else if (c.op == BYDB_OP_IN || c.op == BYDB_OP_NOT_IN) {
-            bool in = !nil && domain_lookup(&c.set, v, len) != GID_NONE;
-            m = c.op == BYDB_OP_IN ? in : !in;
-        } else if (nil) {
-            m = false;      // Compare returns ok=false
-        } else {
-            int cmp;        // sign of literal.Compare(value)
-            if (c.is_int) {
-                if (len != 8) return false;
-                // Go int64 subtraction wraps: take the sign of the
-                // two's-complement difference, not of the true one
-                int64_t d = (int64_t)((uint64_t)c.lit_i -
-                                      (uint64_t)i64_from_cell(v));
-                cmp = d < 0 ? -1 : d > 0 ? 1 : 0;
-            } else {
-                cmp = bytes_compare(c.lit, c.lit_len, v, len);
-            }
-            m = c.op == BYDB_OP_GT   ? cmp < 0
-                : c.op == BYDB_OP_GE ? cmp <= 0
-                : c.op == BYDB_OP_LT ? cmp > 0
-                                     : cmp >= 0;
-        }
-        if (!m) return false;
-    }
+    for (int i = fs.first[slot]; i < fs.first[slot + 1]; i++)
+        if (!cond_match(fs.c[i], v, len, nil)) return false;
     return true;
 }
 
@@ -1474,6 +1476,433 @@ __global__ __launch_bounds__(WAVE) void k_resolve_plain_filter(
             bool match = r.valid && filter_match(fs, slot, ps.vals + r.off,
                                                  r.vlen, r.lp1 == 0);
             uint64_t word = __ballot(match);
+            if (lane == 0) bm[w0 + (base >> 6)] = word;
+        }
+        if (lane == 0) out[bi].rle_bit_off = w0;
+    }
+}
+
+// ---------------- criteria tree resolve ----------------
+// The reference's BuildTagFilter (tag_filter.go:84-142) nests
+// andLogicalNode / orLogicalNode over the per-condition filters; a node
+// folds its children's results left to right (isMatch :259-274) with
+// merge = all (:288-295) or any (:323-330).  The host flattens the tree
+// into a 256-bit truth table indexed by the conditions' result signature
+// (bit i = condition i), so the device never walks a tree: it evaluates
+// leaves with cond_match, assembles the signature and looks one bit up.
+// Every leaf keeps its own nil rule, so NE / NOT_IN leaves are true on nil
+// rows under OR exactly as under AND.
+//
+// Per block, a conditioned slot is CONSTANT (no column: the leaves take
+// their nil result; single-run dictionary: the leaves on the one value) or
+// VARYING (multi-run dictionary, plain column).  Three verdict classes:
+//   no varying slot       one lookup -> CLEAR / SKIP (entity tags)
+//   one varying dict slot per-code lookup -> that slot's code mask, walked
+//                         by the scan's RLE walker (or CLEAR / SKIP when
+//                         the mask is full / empty)
+//   anything else         CLEAR / SKIP when the table is constant over the
+//                         signatures the block can reach, else a ROW-BITMAP
+//                         block: k_resolve_tree_rows writes one match bit
+//                         per row and the scan's bitmap walker consumes it
+//                         as a plain-column predicate on slot 0
+// The scan kernel sees PredBlocks and the flag byte only, as before.
+struct TreeSpec {
+    uint64_t tt[4];     // bit sig: the tree's result
+    uint32_t bits;      // nibble k: signature bit of FilterSet::c[k]
+    uint32_t _p;
+};
+
+__device__ __forceinline__ uint32_t tree_leaf_bit(const TreeSpec &ts, int k) {
+    return 1u << ((ts.bits >> (4 * k)) & 7);
+}
+
+__device__ __forceinline__ bool tree_lookup(const TreeSpec &ts, uint32_t sig) {
+    uint32_t w = (sig >> 6) & 3;
+    uint64_t word = w == 0 ? ts.tt[0] : w == 1 ? ts.tt[1]
+                    : w == 2 ? ts.tt[2] : ts.tt[3];
+    return (word >> (sig & 63)) & 1;
+}
+
+// signature bits one slot's leaves contribute for one tag value
+__device__ uint32_t slot_sig(const FilterSet &fs, const TreeSpec &ts, int slot,
+                             const uint8_t *v, uint64_t len, bool nil) {
+    uint32_t sig = 0;
+    for (int k = fs.first[slot]; k < fs.first[slot + 1]; k++)
+        if (cond_match(fs.c[k], v, len, nil)) sig |= tree_leaf_bit(ts, k);
+    return sig;
+}
+
+#define TK_CONST 0   // contributes fixed signature bits for the whole block
+#define TK_DICT 1    // multi-run dictionary: signature varies by code
+#define TK_PLAIN 2   // plain column: signature varies by row
+#define TK_ERR 3
+
+// Classify one slot of one block; a constant slot ORs its bits into
+// *const_sig, a dictionary slot leaves its parsed header in *ds.
+__device__ __forceinline__ int tree_classify_slot(
+    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
+    const bydb_block_desc *__restrict__ bd, int slot, const FilterSet &fs,
+    const TreeSpec &ts, DictStream *ds, uint32_t *const_sig) {
+    if (fs.first[slot] == fs.first[slot + 1]) return TK_CONST;
+    int kind = tag_open(payload, sidecar, bd, slot, ds);
+    if (kind == TS_NIL) {
+        *const_sig |= slot_sig(fs, ts, slot, nullptr, 0, true);
+        return TK_CONST;
+    }
+    if (kind == TS_ERR || (kind == TS_PLAIN && !ds->in_sidecar)) return TK_ERR;
+    if (kind == TS_PLAIN) return TK_PLAIN;
+    if (ds->count > 256) return TK_ERR;
+    int64_t code = dict_uniform_code(*ds, bd);
+    if (code < 0) return TK_DICT;
+    if ((uint64_t)code >= ds->count) return TK_ERR;
+    uint64_t voff = 0, alen = 0;
+    for (int64_t v = 0; v <= code; v++) {
+        alen = be_len(ds->lens, (uint64_t)v, ds->wbytes);
+        if (v < code) voff += alen ? alen - 1 : 0;
+    }
+    *const_sig |= slot_sig(fs, ts, slot, ds->vals + voff, alen ? alen - 1 : 0,
+                           alen == 0);
+    return TK_CONST;
+}
+
+__device__ __forceinline__ void sigset_add(uint64_t set[4], uint32_t sig) {
+    uint32_t w = (sig >> 6) & 3;
+    uint64_t b = 1ull << (sig & 63);
+    set[0] |= w == 0 ? b : 0;
+    set[1] |= w == 1 ? b : 0;
+    set[2] |= w == 2 ? b : 0;
+    set[3] |= w == 3 ? b : 0;
+}
+
+// next member of a signature set at or above `from`, 256 when none
+__device__ __forceinline__ uint32_t sigset_next(const uint64_t set[4],
+                                                uint32_t from) {
+    for (uint32_t w = from >> 6; w < 4; w++) {
+        uint64_t m = w == 0 ? set[0] : w == 1 ? set[1]
+                     : w == 2 ? set[2] : set[3];
+        if (w == (from >> 6)) m &= ~0ull << (from & 63);
+        if (m) return w * 64 + (uint32_t)__builtin_ctzll(m);
+    }
+    return 256;
+}
+
+// reach := { r | p : r in reach, p in part } — at most 256 pairs, since
+// the slots' signature bits are disjoint
+__device__ __forceinline__ void sigset_cross(uint64_t reach[4],
+                                             const uint64_t part[4]) {
+    uint64_t next[4] = {0, 0, 0, 0};
+    for (uint32_t p = sigset_next(part, 0); p < 256;
+         p = sigset_next(part, p + 1))
+        for (uint32_t r = sigset_next(reach, 0); r < 256;
+             r = sigset_next(reach, r + 1))
+            sigset_add(next, r | p);
+    reach[0] = next[0]; reach[1] = next[1];
+    reach[2] = next[2]; reach[3] = next[3];
+}
+
+// One thread per block: classify, then decide by the truth table.  Writes
+// what k_resolve_filter writes — PredBlock[3][n_blocks], the flag byte, the
+// walk census — plus the per-class block counts in stats[4] (clear, skip,
+// code-mask walk, row-bitmap walk); stats[3] sizes the bitmap arena.
+__global__ void k_resolve_tree(
+    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
+    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
+    FilterSet fs, TreeSpec ts, PredBlock *__restrict__ out,
+    uint8_t *__restrict__ flags, uint32_t *__restrict__ walk_count,
+    uint32_t *__restrict__ stats) {
+    int64_t bi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint8_t f = PF_CLEAR;
+    bool rows_blk = false;
+    if (bi < n_blocks) {
+        const bydb_block_desc *bd = &blocks[bi];
+        PredBlock off;
+        for (int i = 0; i < 4; i++) off.mask[i] = 0;
+        off.rle_bit_off = 0; off.nentries = 0; off.width = 0;
+        off.active = 0; off.err = 0; off.uniform = 0; off.plain = 0;
+        off.disabled = 1;
+        PredBlock walk = off;
+        int walk_slot = -1;
+        uint32_t const_sig = 0;
+        int kinds[3] = {TK_CONST, TK_CONST, TK_CONST};
+        DictStream ds[3];
+        int n_var = 0, var_slot = 0, var_kind = TK_CONST;
+        bool err = false;
+#pragma unroll
+        for (int sl = 0; sl < 3; sl++) {
+            if (sl >= fs.n_slots) continue;
+            kinds[sl] = tree_classify_slot(payload, sidecar, bd, sl, fs, ts,
+                                           &ds[sl], &const_sig);
+            if (kinds[sl] == TK_ERR) err = true;
+            if (kinds[sl] == TK_DICT || kinds[sl] == TK_PLAIN) {
+                n_var++;
+                var_slot = sl;
+                var_kind = kinds[sl];
+            }
+        }
+        if (err) {
+            f = PF_ERR;
+        } else if (n_var == 0) {
+            f = tree_lookup(ts, const_sig) ? PF_CLEAR : PF_SKIP;
+        } else if (n_var == 1 && var_kind == TK_DICT) {
+            // the single-slot shape of resolve_one_filter: one code mask
+            bool any = false, all = true;
+#pragma unroll
+            for (int sl = 0; sl < 3; sl++) {
+                if (sl != var_slot) continue;
+                const DictStream &d = ds[sl];
+                uint64_t voff = 0;
+                for (uint64_t v = 0; v < d.count; v++) {
+                    uint64_t alen = be_len(d.lens, v, d.wbytes);
+                    uint64_t vlen = alen ? alen - 1 : 0;
+                    uint32_t sig = const_sig | slot_sig(fs, ts, sl,
+                                                        d.vals + voff, vlen,
+                                                        alen == 0);
+                    if (tree_lookup(ts, sig)) {
+                        sigset_add(walk.mask, (uint32_t)v);
+                        any = true;
+                    } else {
+                        all = false;
+                    }
+                    voff += vlen;
+                }
+                walk.nentries = d.nentries;
+                walk.width = (uint8_t)d.width;
+                walk.rle_bit_off = dict_rle_bit_off(d);
+            }
+            if (!any) {
+                f = PF_SKIP;
+            } else if (all) {
+                f = PF_CLEAR;
+            } else {
+                f = PF_WALK;
+                walk.active = 1;
+                walk.disabled = 0;
+                walk_slot = var_slot;
+            }
+        } else {
+            // signatures the block can reach: constant bits, times what
+            // each dictionary actually produces, times every combination
+            // of a plain slot's leaves
+            uint64_t reach[4] = {0, 0, 0, 0};
+            sigset_add(reach, const_sig);
+#pragma unroll
+            for (int sl = 0; sl < 3; sl++) {
+                if (kinds[sl] != TK_DICT && kinds[sl] != TK_PLAIN) continue;
+                uint64_t part[4] = {0, 0, 0, 0};   // this slot's signatures
+                if (kinds[sl] == TK_DICT) {
+                    uint64_t voff = 0;
+                    for (uint64_t v = 0; v < ds[sl].count; v++) {
+                        uint64_t alen = be_len(ds[sl].lens, v, ds[sl].wbytes);
+                        uint64_t vlen = alen ? alen - 1 : 0;
+                        sigset_add(part, slot_sig(fs, ts, sl,
+                                                  ds[sl].vals + voff, vlen,
+                                                  alen == 0));
+                        voff += vlen;
+                    }
+                } else {
+                    uint32_t m = 0;
+                    for (int k = fs.first[sl]; k < fs.first[sl + 1]; k++)
+                        m |= tree_leaf_bit(ts, k);
+                    uint32_t sub = 0;
+                    do {          // every subset of the slot's leaf bits
+                        sigset_add(part, sub);
+                        sub = (sub - m) & m;
+                    } while (sub != 0);
+                }
+                sigset_cross(reach, part);
+            }
+            bool any = false, all = true;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                if (reach[i] & ts.tt[i]) any = true;
+                if (reach[i] & ~ts.tt[i]) all = false;
+            }
+            if (!any) {
+                f = PF_SKIP;
+            } else if (all) {
+                f = PF_CLEAR;
+            } else {
+                // row-bitmap block: slot 0 carries the bitmap as a plain
+                // predicate; k_resolve_tree_rows fills rle_bit_off
+                f = PF_WALK;
+                rows_blk = true;
+                walk.active = 1;
+                walk.plain = 1;
+                walk.disabled = 0;
+                walk_slot = 0;
+            }
+        }
+        if (f == PF_ERR) off.err = 1;
+#pragma unroll
+        for (int sl = 0; sl < 3; sl++)
+            if (sl < fs.n_slots) {
+                if (sl == walk_slot) out[(int64_t)sl * n_blocks + bi] = walk;
+                else out[(int64_t)sl * n_blocks + bi] = off;
+            }
+        flags[bi] = f;
+    }
+    const bool live = bi < n_blocks;
+    uint64_t wmask = __ballot(live && f == PF_WALK);
+    uint64_t rmask = __ballot(live && rows_blk);
+    uint64_t cmask = __ballot(live && f == PF_CLEAR);
+    uint64_t smask = __ballot(live && f == PF_SKIP);
+    if ((threadIdx.x & 63) == 0) {
+        if (wmask) atomicAdd(walk_count, (uint32_t)__popcll(wmask));
+        if (cmask) atomicAdd(&stats[0], (uint32_t)__popcll(cmask));
+        if (smask) atomicAdd(&stats[1], (uint32_t)__popcll(smask));
+        if (wmask & ~rmask)
+            atomicAdd(&stats[2], (uint32_t)__popcll(wmask & ~rmask));
+        if (rmask) atomicAdd(&stats[3], (uint32_t)__popcll(rmask));
+    }
+}
+
+// wave-uniform forward cursor over a dictionary slot's bit-packed RLE runs
+struct CodeWalk {
+    const uint8_t *base;
+    uint64_t bit0;
+    uint32_t nentries, width;
+    uint32_t entry;            // next entry index (2 per run)
+    int64_t run_lo, run_hi;    // rows [run_lo, run_hi) of the current run
+    uint32_t run_code;
+};
+
+#define CODE_NONE 0xFFFFFFFFu  // row past the last run
+
+// The dictionary code of each lane's row (rows ascend across calls): the
+// shape of pred_match_rows, returning the run's code instead of its match.
+__device__ __forceinline__ uint32_t code_of_rows(CodeWalk *cw, int64_t row,
+                                                 bool need) {
+    uint32_t code = CODE_NONE;
+    while (true) {
+        bool mine = need && row >= cw->run_lo && row < cw->run_hi;
+        if (mine) { code = cw->run_code; need = false; }
+        if (__all(!need)) break;
+        if (cw->entry + 1 >= cw->nentries) {   // RLE exhausted
+            cw->run_lo = cw->run_hi;
+            cw->run_hi = INT64_MAX;
+            cw->run_code = CODE_NONE;
+            continue;
+        }
+        uint64_t c = rd_bits_be(cw->base,
+                                cw->bit0 + (uint64_t)cw->entry * cw->width,
+                                cw->width);
+        uint64_t cnt = rd_bits_be(
+            cw->base, cw->bit0 + (uint64_t)(cw->entry + 1) * cw->width,
+            cw->width);
+        cw->entry += 2;
+        cw->run_lo = cw->run_hi;
+        cw->run_hi += (int64_t)cnt;
+        cw->run_code = (uint32_t)c;
+    }
+    return code;
+}
+
+// Row-bitmap stage: one wave per row-bitmap block.  Setup re-classifies
+// the block's slots (cheap, wave-uniform), claims a 128-word bitmap and
+// builds a code -> signature byte table in LDS per varying dictionary slot
+// (lanes take dictionary values lane, lane+64, ...; value offsets come
+// from the wave prefix scan in plain_chunk over the dictionary's length
+// list).  Then 64 rows per step: each lane gets its row's code from the
+// forward RLE cursor (dictionary slots) or its row's value (plain slots),
+// assembles the signature, looks the truth table up, and the ballot is the
+// bitmap word.  Rows whose code no run covers, or whose code the
+// dictionary does not define, match nothing — the RLE walker's no-match
+// tail.  That is a rule for malformed streams only (runs that do not add
+// up to the block's row count), and on such a block the two kernels can
+// disagree: k_resolve_tree reasons over dictionary values, not rows, so it
+// may call the block CLEAR (say through a NE leaf on another slot) where
+// this kernel, had the block reached it, would drop the uncovered rows.
+// Unparseable streams, over-long blocks and an exhausted arena set
+// err and turn the block's flag byte to PF_ERR, which the scan reports.
+__global__ __launch_bounds__(WAVE) void k_resolve_tree_rows(
+    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
+    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
+    FilterSet fs, TreeSpec ts, PredBlock *__restrict__ out,
+    uint8_t *__restrict__ flags, uint64_t *__restrict__ bm,
+    uint32_t *__restrict__ ctr, uint64_t bm_cap_streams) {
+    __shared__ uint8_t sigtab[3][256];
+    const int lane = threadIdx.x;
+    for (int64_t bi = blockIdx.x; bi < n_blocks; bi += gridDim.x) {
+        if (flags[bi] != PF_WALK || !out[bi].plain) continue;
+        const bydb_block_desc *bd = &blocks[bi];
+        const uint64_t n = bd->count;
+        uint32_t const_sig = 0;
+        int kinds[3] = {TK_CONST, TK_CONST, TK_CONST};
+        DictStream ds[3];
+        PlainStream ps[3];
+        CodeWalk cw[3];
+        uint64_t carry[3] = {0, 0, 0};
+        bool bad = n > (uint64_t)PLAIN_BM_WORDS * 64;
+#pragma unroll
+        for (int sl = 0; sl < 3; sl++) {
+            if (sl >= fs.n_slots) continue;
+            kinds[sl] = tree_classify_slot(payload, sidecar, bd, sl, fs, ts,
+                                           &ds[sl], &const_sig);
+            if (kinds[sl] == TK_ERR) bad = true;
+            if (kinds[sl] == TK_PLAIN &&
+                !plain_open(payload, sidecar, bd, sl, &ps[sl]))
+                bad = true;
+        }
+        uint32_t slot_id = 0;
+        if (!bad) {
+            slot_id = claim_stream_slot(ctr, lane);
+            if (slot_id >= bm_cap_streams) bad = true;  // arena exhausted
+        }
+        if (bad) {
+            if (lane == 0) {
+                out[bi].err = 1;
+                flags[bi] = PF_ERR;
+            }
+            continue;
+        }
+        __syncthreads();   // the previous block's table reads are done
+#pragma unroll
+        for (int sl = 0; sl < 3; sl++) {
+            if (kinds[sl] != TK_DICT) continue;
+            PlainStream dv;    // the dictionary's value list, read as rows
+            dv.lens = ds[sl].lens;
+            dv.vals = ds[sl].vals;
+            dv.n = ds[sl].count;
+            dv.wbytes = ds[sl].wbytes;
+            uint64_t dcarry = 0;
+            for (uint64_t base = 0; base < dv.n; base += WAVE) {
+                PlainRow r = plain_chunk(dv, base, lane, &dcarry);
+                if (r.valid)
+                    sigtab[sl][base + (uint64_t)lane] = (uint8_t)slot_sig(
+                        fs, ts, sl, dv.vals + r.off, r.vlen, r.lp1 == 0);
+            }
+            cw[sl].base = ds[sl].base;
+            cw[sl].bit0 = ds[sl].bit0;
+            cw[sl].nentries = ds[sl].nentries;
+            cw[sl].width = ds[sl].width;
+            cw[sl].entry = 0;
+            cw[sl].run_lo = 0;
+            cw[sl].run_hi = 0;
+            cw[sl].run_code = CODE_NONE;
+        }
+        __syncthreads();
+        const uint64_t w0 = (uint64_t)slot_id * PLAIN_BM_WORDS;
+        for (uint64_t base = 0; base < n; base += WAVE) {
+            const uint64_t row = base + (uint64_t)lane;
+            const bool valid = row < n;
+            uint32_t sig = const_sig;
+            bool ok = valid;
+#pragma unroll
+            for (int sl = 0; sl < 3; sl++) {
+                if (kinds[sl] == TK_DICT) {
+                    uint32_t code = code_of_rows(&cw[sl], (int64_t)row, valid);
+                    if ((uint64_t)code < ds[sl].count)
+                        sig |= sigtab[sl][code];
+                    else
+                        ok = false;
+                } else if (kinds[sl] == TK_PLAIN) {
+                    PlainRow r = plain_chunk(ps[sl], base, lane, &carry[sl]);
+                    if (r.valid)
+                        sig |= slot_sig(fs, ts, sl, ps[sl].vals + r.off,
+                                        r.vlen, r.lp1 == 0);
+                }
+            }
+            uint64_t word = __ballot(ok && tree_lookup(ts, sig));
             if (lane == 0) bm[w0 + (base >> 6)] = word;
         }
         if (lane == 0) out[bi].rle_bit_off = w0;
@@ -3368,6 +3797,10 @@ struct bydb_session {
     uint8_t *d_pred_flags = nullptr;
     int64_t pred_flags_cap = 0;
     uint32_t *d_walk_count = nullptr;
+    // criteria trees: per-class block counts of the last tree consume
+    // (k_resolve_tree), read back once on the OR path
+    uint32_t *d_tree_stats = nullptr;
+    uint64_t tree_stats[4] = {0, 0, 0, 0};
     uint64_t *d_first_seen = nullptr;
     uint64_t first_seen_cap = 0;
     float last_ms = 0.0f;
@@ -3437,6 +3870,7 @@ extern "C" void bydb_session_destroy(bydb_session *s) {
     if (s->d_pred_bm) (void)hipFree(s->d_pred_bm);
     if (s->d_pred_flags) (void)hipFree(s->d_pred_flags);
     if (s->d_walk_count) (void)hipFree(s->d_walk_count);
+    if (s->d_tree_stats) (void)hipFree(s->d_tree_stats);
     if (s->d_first_seen) (void)hipFree(s->d_first_seen);
     if (s->ev_start) (void)hipEventDestroy(s->ev_start);
     if (s->ev_stop) (void)hipEventDestroy(s->ev_stop);
@@ -3957,14 +4391,10 @@ extern "C" int bydb_consume(bydb_session *s, int64_t min_ts, int64_t max_ts,
 static int consume_conds(bydb_session *s, int64_t min_ts, int64_t max_ts,
                          const bydb_tag_cond *conds, int n_conds);
 
-// Scan under ANDed tag conditions (header: "tag filter operators"): the
-// public entry point validates, consume_conds does the work.
-extern "C" int bydb_consume_filter(bydb_session *s, int64_t min_ts,
-                                   int64_t max_ts, const bydb_tag_cond *conds,
-                                   int n_conds) {
-    HIP_TRY(s, hipSetDevice(s->device));
-    if (!s->d_acc) { s->err = "configure first"; return BYDB_ERR_STATE; }
-    if (s->n_blocks == 0) { s->err = "no part resident"; return BYDB_ERR_STATE; }
+// The argument rules every condition-taking entry point shares (header:
+// "tag filter operators").
+static int validate_conds(bydb_session *s, const bydb_tag_cond *conds,
+                          int n_conds) {
     if (n_conds < 0 || n_conds > BYDB_FILTER_MAX_CONDS ||
         (n_conds > 0 && conds == nullptr)) {
         s->err = "n_conds must be 0..8";
@@ -4016,24 +4446,35 @@ extern "C" int bydb_consume_filter(bydb_session *s, int64_t min_ts,
             return BYDB_ERR_BAD_ARG;
         }
     }
+    return BYDB_OK;
+}
+
+// Scan under ANDed tag conditions (header: "tag filter operators"): the
+// public entry point validates, consume_conds does the work.
+extern "C" int bydb_consume_filter(bydb_session *s, int64_t min_ts,
+                                   int64_t max_ts, const bydb_tag_cond *conds,
+                                   int n_conds) {
+    HIP_TRY(s, hipSetDevice(s->device));
+    if (!s->d_acc) { s->err = "configure first"; return BYDB_ERR_STATE; }
+    if (s->n_blocks == 0) { s->err = "no part resident"; return BYDB_ERR_STATE; }
+    int rc = validate_conds(s, conds, n_conds);
+    if (rc != BYDB_OK) return rc;
     return consume_conds(s, min_ts, max_ts, conds, n_conds);
 }
 
-// The one resolve stage behind every consume entry point, over conditions
-// already validated.  The host sorts the conditions by slot and uploads one
-// arena — u64 section (set value offsets, set hashes), u32 section (set
-// slots), byte section (literals and set values) — in a single copy.  IN /
-// NOT_IN lists become the open-addressing table the group-by domain uses,
-// so the device probes once per value instead of comparing n_values times.
-// The two resolves then feed the scan launch.
-static int consume_conds(bydb_session *s, int64_t min_ts, int64_t max_ts,
-                         const bydb_tag_cond *conds, int n_conds) {
-    if (n_conds == 0) return launch_scan(s, min_ts, max_ts, nullptr, 0);
-
+// The device form of validated conditions (n_conds >= 1).  The host sorts
+// the conditions by slot — order[k] is the caller's index of FilterSet
+// condition k — and uploads one arena — u64 section (set value offsets,
+// set hashes), u32 section (set slots), byte section (literals and set
+// values) — in a single copy.  IN / NOT_IN lists become the
+// open-addressing table the group-by domain uses, so the device probes
+// once per value instead of comparing n_values times.
+static int build_filter_set(bydb_session *s, const bydb_tag_cond *conds,
+                            int n_conds, FilterSet *fs_out,
+                            int order[BYDB_FILTER_MAX_CONDS]) {
     // conditions sorted by slot (stable), arena sections built on the host
-    int order[BYDB_FILTER_MAX_CONDS];
     int n_ord = 0;
-    FilterSet fs;
+    FilterSet &fs = *fs_out;
     memset(&fs, 0, sizeof(fs));
     for (int sl = 0; sl < 3; sl++) {
         fs.first[sl] = n_ord;
@@ -4125,7 +4566,19 @@ static int consume_conds(bydb_session *s, int64_t min_ts, int64_t max_ts,
             }
         }
     }
-    int rc = ensure_pred_buffers(s);
+    return BYDB_OK;
+}
+
+// The one resolve stage behind every conjunctive consume entry point, over
+// conditions already validated: the two resolves feed the scan launch.
+static int consume_conds(bydb_session *s, int64_t min_ts, int64_t max_ts,
+                         const bydb_tag_cond *conds, int n_conds) {
+    if (n_conds == 0) return launch_scan(s, min_ts, max_ts, nullptr, 0);
+    FilterSet fs;
+    int order[BYDB_FILTER_MAX_CONDS];
+    int rc = build_filter_set(s, conds, n_conds, &fs, order);
+    if (rc != BYDB_OK) return rc;
+    rc = ensure_pred_buffers(s);
     if (rc != BYDB_OK) return rc;
     const int rthreads = 256;
     const int rblocks = (int)((s->n_blocks + rthreads - 1) / rthreads);
@@ -4155,6 +4608,173 @@ static int consume_conds(bydb_session *s, int64_t min_ts, int64_t max_ts,
                                s->d_pred_bm, s->d_plain_ctr, s->n_plain_host);
             HIP_TRY(s, hipGetLastError());
         }
+    }
+    return launch_scan(s, min_ts, max_ts, s->d_preds, fs.n_slots);
+}
+
+// ---- criteria trees (header: "AND / OR criteria trees") ----
+// Validate a post-order tree and evaluate it for every assignment of its
+// leaves at once: a node's value is a 256-bit vector over signatures, a
+// leaf's is "bit c of the signature", AND / OR are bitwise.  Pure host.
+static int tree_table(const bydb_filter_node *nodes, int n_nodes, int n_conds,
+                      uint64_t table[4], bool *has_or, const char **why) {
+    struct Bits { uint64_t w[4]; };
+    static const uint64_t kLeaf[6] = {
+        0xAAAAAAAAAAAAAAAAull, 0xCCCCCCCCCCCCCCCCull, 0xF0F0F0F0F0F0F0F0ull,
+        0xFF00FF00FF00FF00ull, 0xFFFF0000FFFF0000ull, 0xFFFFFFFF00000000ull};
+    *has_or = false;
+    if (n_conds < 1 || n_conds > BYDB_FILTER_MAX_CONDS) {
+        *why = "a filter tree takes 1..8 conditions";
+        return BYDB_ERR_BAD_ARG;
+    }
+    if (n_nodes != 2 * n_conds - 1 || nodes == nullptr || table == nullptr) {
+        *why = "filter tree needs n_nodes == 2 * n_conds - 1";
+        return BYDB_ERR_BAD_ARG;
+    }
+    Bits val[2 * BYDB_FILTER_MAX_CONDS - 1];
+    bool cond_used[BYDB_FILTER_MAX_CONDS] = {};
+    bool has_parent[2 * BYDB_FILTER_MAX_CONDS - 1] = {};
+    // signatures that exist: the low 2^n_conds bits
+    Bits live;
+    for (int w = 0; w < 4; w++) {
+        int64_t bits = ((int64_t)1 << n_conds) - 64 * w;
+        live.w[w] = bits >= 64 ? ~0ull : bits <= 0 ? 0 : (1ull << bits) - 1;
+    }
+    for (int i = 0; i < n_nodes; i++) {
+        const bydb_filter_node &nd = nodes[i];
+        if (nd.op == BYDB_NODE_LEAF) {
+            if (nd.left < 0 || nd.left >= n_conds) {
+                *why = "filter tree leaf names no condition";
+                return BYDB_ERR_BAD_ARG;
+            }
+            if (cond_used[nd.left]) {
+                *why = "filter tree references a condition twice";
+                return BYDB_ERR_BAD_ARG;
+            }
+            cond_used[nd.left] = true;
+            for (int w = 0; w < 4; w++) {
+                uint64_t v = nd.left < 6 ? kLeaf[nd.left]
+                             : nd.left == 6 ? ((w & 1) ? ~0ull : 0)
+                                            : ((w & 2) ? ~0ull : 0);
+                val[i].w[w] = v & live.w[w];
+            }
+        } else if (nd.op == BYDB_NODE_AND || nd.op == BYDB_NODE_OR) {
+            if (nd.left < 0 || nd.left >= i || nd.right < 0 || nd.right >= i) {
+                *why = "filter tree child index must be below its parent's";
+                return BYDB_ERR_BAD_ARG;
+            }
+            if (nd.left == nd.right || has_parent[nd.left] ||
+                has_parent[nd.right]) {
+                *why = "filter tree node has two parents";
+                return BYDB_ERR_BAD_ARG;
+            }
+            has_parent[nd.left] = has_parent[nd.right] = true;
+            if (nd.op == BYDB_NODE_OR) *has_or = true;
+            for (int w = 0; w < 4; w++)
+                val[i].w[w] = nd.op == BYDB_NODE_AND
+                                  ? val[nd.left].w[w] & val[nd.right].w[w]
+                                  : val[nd.left].w[w] | val[nd.right].w[w];
+        } else {
+            *why = "unknown filter tree node op";
+            return BYDB_ERR_BAD_ARG;
+        }
+    }
+    for (int c = 0; c < n_conds; c++)
+        if (!cond_used[c]) {
+            *why = "filter tree never references a condition";
+            return BYDB_ERR_BAD_ARG;
+        }
+    for (int i = 0; i + 1 < n_nodes; i++)
+        if (!has_parent[i]) {
+            *why = "filter tree node has no parent";
+            return BYDB_ERR_BAD_ARG;
+        }
+    for (int w = 0; w < 4; w++) table[w] = val[n_nodes - 1].w[w];
+    return BYDB_OK;
+}
+
+extern "C" int bydb_filter_tree_table(const bydb_filter_node *nodes,
+                                      int n_nodes, int n_conds,
+                                      uint64_t table[4]) {
+    bool has_or;
+    const char *why;
+    return tree_table(nodes, n_nodes, n_conds, table, &has_or, &why);
+}
+
+extern "C" int bydb_filter_tree_stats(bydb_session *s, uint64_t out[4]) {
+    for (int i = 0; i < 4; i++) out[i] = s->tree_stats[i];
+    return BYDB_OK;
+}
+
+// Scan under a criteria tree.  A tree without an OR node is the
+// conjunction consume_conds already resolves.  Otherwise k_resolve_tree
+// classifies every block; its row-bitmap census is read back — the one
+// host wait of this path — to size the bitmap arena, k_resolve_tree_rows
+// fills the bitmaps, and the unchanged scan launch consumes the result.
+extern "C" int bydb_consume_filter_tree(bydb_session *s, int64_t min_ts,
+                                        int64_t max_ts,
+                                        const bydb_tag_cond *conds, int n_conds,
+                                        const bydb_filter_node *nodes,
+                                        int n_nodes) {
+    HIP_TRY(s, hipSetDevice(s->device));
+    if (!s->d_acc) { s->err = "configure first"; return BYDB_ERR_STATE; }
+    if (s->n_blocks == 0) { s->err = "no part resident"; return BYDB_ERR_STATE; }
+    for (int i = 0; i < 4; i++) s->tree_stats[i] = 0;
+    if (n_conds == 0 && n_nodes == 0)
+        return consume_conds(s, min_ts, max_ts, nullptr, 0);
+    int rc = validate_conds(s, conds, n_conds);
+    if (rc != BYDB_OK) return rc;
+    TreeSpec ts;
+    memset(&ts, 0, sizeof(ts));
+    bool has_or = false;
+    const char *why = "";
+    rc = tree_table(nodes, n_nodes, n_conds, ts.tt, &has_or, &why);
+    if (rc != BYDB_OK) { s->err = why; return rc; }
+    if (!has_or) return consume_conds(s, min_ts, max_ts, conds, n_conds);
+
+    FilterSet fs;
+    int order[BYDB_FILTER_MAX_CONDS];
+    rc = build_filter_set(s, conds, n_conds, &fs, order);
+    if (rc != BYDB_OK) return rc;
+    for (int k = 0; k < n_conds; k++) ts.bits |= (uint32_t)order[k] << (4 * k);
+    rc = ensure_pred_buffers(s);
+    if (rc != BYDB_OK) return rc;
+    if (!s->d_tree_stats)
+        HIP_TRY(s, hipMalloc(&s->d_tree_stats, 4 * sizeof(uint32_t)));
+    HIP_TRY(s, hipMemsetAsync(s->d_tree_stats, 0, 4 * sizeof(uint32_t),
+                              s->stream));
+    const int rthreads = 256;
+    const int rblocks = (int)((s->n_blocks + rthreads - 1) / rthreads);
+    hipLaunchKernelGGL(k_resolve_tree, dim3(rblocks), dim3(rthreads), 0,
+                       s->stream, s->d_payload, s->d_sidecar, s->d_blocks,
+                       s->n_blocks, fs, ts, s->d_preds, s->d_pred_flags,
+                       s->d_walk_count, s->d_tree_stats);
+    HIP_TRY(s, hipGetLastError());
+    uint32_t h_stats[4] = {0, 0, 0, 0};
+    HIP_TRY(s, hipMemcpyAsync(h_stats, s->d_tree_stats, sizeof(h_stats),
+                              hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    for (int i = 0; i < 4; i++) s->tree_stats[i] = h_stats[i];
+    const uint64_t n_row_blocks = h_stats[3];
+    if (n_row_blocks > 0) {
+        // one bitmap per row-bitmap block; the arena only grows and is
+        // shared with the plain-column bitmaps of consume_conds
+        uint64_t words = n_row_blocks * PLAIN_BM_WORDS;
+        if (words > s->pred_bm_cap) {
+            if (s->d_pred_bm) { (void)hipFree(s->d_pred_bm); s->d_pred_bm = nullptr; }
+            s->pred_bm_cap = 0;
+            HIP_TRY(s, hipMalloc(&s->d_pred_bm, words * sizeof(uint64_t)));
+            s->pred_bm_cap = words;
+        }
+        HIP_TRY(s, hipMemsetAsync(s->d_plain_ctr, 0, sizeof(uint32_t),
+                                  s->stream));
+        int pgrid = (int)(s->n_blocks < 65535 ? s->n_blocks : 65535);
+        hipLaunchKernelGGL(k_resolve_tree_rows, dim3(pgrid), dim3(WAVE), 0,
+                           s->stream, s->d_payload, s->d_sidecar, s->d_blocks,
+                           s->n_blocks, fs, ts, s->d_preds, s->d_pred_flags,
+                           s->d_pred_bm, s->d_plain_ctr,
+                           s->pred_bm_cap / PLAIN_BM_WORDS);
+        HIP_TRY(s, hipGetLastError());
     }
     return launch_scan(s, min_ts, max_ts, s->d_preds, fs.n_slots);
 }

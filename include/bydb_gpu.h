@@ -215,9 +215,9 @@ int bydb_consume_multi(bydb_session *s, int64_t min_ts, int64_t max_ts,
  * passed as the stored 8-byte cell; EQ/NE/IN/NOT_IN compare cells by
  * bytes for both tag types.
  *
- * Conditions are ANDed (andLogicalNode); several may target one slot
- * (200 <= code < 300 is two).  OR across conditions is out of scope: a
- * host with an OR tree keeps that query on its CPU path. */
+ * bydb_consume_filter ANDs its conditions (andLogicalNode); several may
+ * target one slot (200 <= code < 300 is two).  AND / OR criteria trees over
+ * the same conditions go through bydb_consume_filter_tree below. */
 enum {
     BYDB_OP_EQ = 1,
     BYDB_OP_NE = 2,
@@ -253,6 +253,71 @@ typedef struct {
  * carries more than BYDB_FILTER_MAX_VALUES values in total. */
 int bydb_consume_filter(bydb_session *s, int64_t min_ts, int64_t max_ts,
                         const bydb_tag_cond *conds, int n_conds);
+
+/* ---- AND / OR criteria trees over tag conditions ----
+ * BuildTagFilter (pkg/query/logical/tag_filter.go:84-142) turns a
+ * modelv1.Criteria into a binary tree of andLogicalNode / orLogicalNode
+ * over the per-condition filters above.  A node's Match is isMatch
+ * (:259-274): its children are evaluated left to right and folded with the
+ * node's merge — andLogicalNode.merge (:288-295) is true when every input
+ * is, orLogicalNode.merge (:323-330) when any input is.  Leaves keep their
+ * own nil rule under either node: NE / NOT_IN are true on a nil row, so
+ * `NE x OR ...` selects every nil row, and `EQ x OR NE y` selects a nil row
+ * through its right leaf.
+ *
+ * The reference drops DummyFilter children (conditions on entity tags it
+ * resolves through the series index, skipped tag names) before the tree is
+ * built: logicalNode.append ignores them (:251-257), and a node whose two
+ * children are both dummy is itself dummy (:124-126).  A host does the
+ * same before calling: a node left with one child is replaced by that
+ * child, so the tree passed here is a proper binary tree over the
+ * conditions that remain.  Trees with more than BYDB_FILTER_MAX_CONDS
+ * leaves stay on the host.
+ *
+ * Encoding: `nodes` is the tree in post-order — both children of a node
+ * have smaller indices than the node, the root is the last node.  A LEAF's
+ * `left` is an index into `conds` (`right` is unused, 0); an AND / OR
+ * node's `left` / `right` are node indices.  n_nodes == 2 * n_conds - 1,
+ * every condition is referenced by exactly one leaf and every node but the
+ * root by exactly one parent.  BYDB_NODE_AND / BYDB_NODE_OR carry the
+ * values of modelv1.LogicalExpression.LogicalOp (query.proto:93-95). */
+enum { BYDB_NODE_LEAF = 0, BYDB_NODE_AND = 1, BYDB_NODE_OR = 2 };
+
+typedef struct {
+    int32_t op;     /* BYDB_NODE_* */
+    int32_t left;   /* LEAF: condition index; AND / OR: node index */
+    int32_t right;  /* LEAF: unused (0);      AND / OR: node index */
+} bydb_filter_node;
+
+/* Scan under a criteria tree.  Same asynchronous and sticky-error contract
+ * as bydb_consume_filter, and the same rules for every condition;
+ * n_conds == 0 with n_nodes == 0 is an unfiltered scan.  BYDB_ERR_BAD_ARG
+ * (session stays usable) when n_conds is outside
+ * 1..BYDB_FILTER_MAX_CONDS, n_nodes != 2 * n_conds - 1, a node's op is
+ * unknown, a child index is not below its parent's, a condition is
+ * referenced twice or never, or a node has two parents.  A tree without an
+ * OR node takes exactly the bydb_consume_filter path.  A tree with one
+ * waits once for its resolve stage (to size the row-bitmap arena) before
+ * the scan is launched; the scan itself stays asynchronous. */
+int bydb_consume_filter_tree(bydb_session *s, int64_t min_ts, int64_t max_ts,
+                             const bydb_tag_cond *conds, int n_conds,
+                             const bydb_filter_node *nodes, int n_nodes);
+
+/* Pure host, no GPU: validate the tree (rules above) and write its truth
+ * table.  Bit `sig` of the 256-bit table (word sig >> 6, bit sig & 63) is
+ * the tree's result when condition i evaluates to bit i of `sig`; bits at
+ * and above 2^n_conds are zero.  The device evaluates trees through this
+ * table alone.  BYDB_OK or BYDB_ERR_BAD_ARG. */
+int bydb_filter_tree_table(const bydb_filter_node *nodes, int n_nodes,
+                           int n_conds, uint64_t table[4]);
+
+/* How the blocks of the last bydb_consume_filter_tree call resolved:
+ * out[0] every row matches (folded unpredicated), out[1] no row matches
+ * (skipped), out[2] walked through one slot's dictionary code mask, out[3]
+ * walked through a per-row match bitmap.  All zero after a tree without an
+ * OR node (the bydb_consume_filter path keeps no census) and after an
+ * unfiltered scan. */
+int bydb_filter_tree_stats(bydb_session *s, uint64_t out[4]);
 
 /* ---- finalize + emit (Finalize/NextBatch) ----
  * Syncs the stream, downloads partials and finalises per-group results
