@@ -16,6 +16,7 @@ VT_INT64 = 2
 VT_FLOAT64 = 3
 AGG_SUM, AGG_COUNT, AGG_MIN, AGG_MAX, AGG_MEAN = range(5)
 MODE_ALL, MODE_MAP, MODE_REDUCE = range(3)
+STREAM_AUTO, STREAM_CACHED, STREAM_STREAMING = range(3)
 INT64_MIN = -(2 ** 63)
 FLOAT_RAW_EXP = -32768  # sessions over nullable float64 columns
 INT64_MAX = 2 ** 63 - 1
@@ -300,6 +301,10 @@ def _load():
     lib.bydb_finalize_partials.argtypes = [C.c_void_p, C.POINTER(Partial), C.c_int64]
     lib.bydb_set_float_exp.restype = C.c_int
     lib.bydb_set_float_exp.argtypes = [C.c_void_p, C.c_int16]
+    lib.bydb_set_stream_policy.restype = C.c_int
+    lib.bydb_set_stream_policy.argtypes = [C.c_void_p, C.c_int]
+    lib.bydb_stream_policy_pick.restype = C.c_int
+    lib.bydb_stream_policy_pick.argtypes = [C.c_int, C.c_uint64]
     lib.bydb_last_consume_ms.restype = C.c_double
     lib.bydb_last_consume_ms.argtypes = [C.c_void_p]
     lib.bydb_group_first_seen.restype = C.c_int
@@ -665,6 +670,11 @@ class Session:
         out = (Partial * self.n_groups)()
         self._ck(_lib.bydb_finalize_partials(self._h, out, self.n_groups))
         return list(out)
+
+    def set_stream_policy(self, policy):
+        """STREAM_AUTO (default), STREAM_CACHED or STREAM_STREAMING: how
+        the closed-form scan loads the dense delta streams."""
+        self._ck(_lib.bydb_set_stream_policy(self._h, policy))
 
     def last_consume_ms(self):
         return _lib.bydb_last_consume_ms(self._h)

@@ -355,7 +355,12 @@ __device__ __forceinline__ void dense_fold16(u32x4 w, int32_t *T, int32_t *K) {
 // Per-lane accumulators stay in int32 for a whole batch: with NB = 9,
 // <= 144 bytes/lane * |d| <= 64 * batch-relative offset <= 9215 is about
 // 8.5e7 < 2^31; the batch base is applied in int64.
-template <int NB>
+// NT: the chunk loads are non-temporal (global_load_dwordx4 ... nt).  For
+// a pass over more payload than the last-level cache holds, every line is
+// read once and installing it in the caches only evicts what could still
+// be reused; a part that fits is served from that cache pass after pass
+// and keeps the plain loads (see bydb_stream_policy_pick).
+template <int NB, bool NT>
 __device__ __forceinline__ void dense_region_t(
     const uint8_t *stream, int64_t lo, int64_t hi, int lane,
     int64_t *out_sum_d, int64_t *out_sum_jd) {
@@ -379,6 +384,9 @@ __device__ __forceinline__ void dense_region_t(
         const int32_t lo_rel = lo > a0 ? (int32_t)(lo - a0) : 0;
         const int nch = (hi_rel + DENSE_CHUNK_BYTES - 1) / DENSE_CHUNK_BYTES;
         int32_t acc_d = 0, acc_c = 0, acc_k = 0;
+        auto load = [&](int c) -> u32x4 {
+            return NT ? __builtin_nontemporal_load(p + c * 64) : p[c * 64];
+        };
         auto fold = [&](int c, u32x4 v, bool may_mask) {
             if (may_mask && ((c == 0 && lo_rel > 0) ||
                              (c + 1) * DENSE_CHUNK_BYTES > hi_rel)) {
@@ -401,10 +409,10 @@ __device__ __forceinline__ void dense_region_t(
             // chunk 0 (head) and chunk NB-2 (tail) can need a mask here,
             // chunk NB-1 is folded below and always takes the tail mask
 #pragma unroll
-            for (int c = 0; c < NB - 1; c++) w[c] = p[c * 64];
+            for (int c = 0; c < NB - 1; c++) w[c] = load(c);
             w[NB - 1] = u32x4{0, 0, 0, 0};
             if ((NB - 1) * DENSE_CHUNK_BYTES + lane_off < hi_rel)
-                w[NB - 1] = p[(NB - 1) * 64];
+                w[NB - 1] = load(NB - 1);
 #pragma unroll
             for (int c = 0; c < NB - 1; c++) {
                 fold(c, w[c], c == 0 || c == NB - 2);
@@ -425,7 +433,7 @@ __device__ __forceinline__ void dense_region_t(
             for (int c = 0; c < NB - 2; c++) {
                 w[c] = u32x4{0, 0, 0, 0};
                 if (c * DENSE_CHUNK_BYTES + lane_off < hi_rel)
-                    w[c] = p[c * 64];
+                    w[c] = load(c);
             }
 #pragma unroll
             for (int c = 0; c < NB - 2; c++)
@@ -442,8 +450,8 @@ __device__ __forceinline__ void dense_region_t(
 
 __device__ void dense_region(const uint8_t *stream, int64_t lo, int64_t hi,
                              int lane, int64_t *out_sum_d, int64_t *out_sum_jd) {
-    dense_region_t<DENSE_CHUNKS_CALL>(stream, lo, hi, lane, out_sum_d,
-                                      out_sum_jd);
+    dense_region_t<DENSE_CHUNKS_CALL, false>(stream, lo, hi, lane, out_sum_d,
+                                             out_sum_jd);
 }
 
 // wave-wide inclusive scan of an int32 (per-window lane sums)
@@ -528,7 +536,7 @@ __device__ void dense_minmax(const uint8_t *stream, int64_t b_lo, int64_t b_hi,
 //   region1 bytes [0, min(r0,jend)):          contributes nsel * S1d
 //   region2 bytes [min(r0,jend), jend):       contributes (r1+1)*S2d - S2jd'
 // where S2jd' uses delta index j = bidx+1.
-template <int NB>
+template <int NB, bool NT>
 __device__ __forceinline__ uint64_t dense_delta_weighted_t(
     const uint8_t *stream, int64_t n_deltas, int64_t r0, int64_t r1,
     int lane) {
@@ -538,8 +546,8 @@ __device__ __forceinline__ uint64_t dense_delta_weighted_t(
     int64_t b1 = r0 < jend ? r0 : jend;  // deltas 1..b1 have weight nsel
     int64_t s1d = 0, s1jd = 0, s2d, s2jd;
     // whole-range queries have r0 == 0: no constant-weight region to read
-    if (b1 > 0) dense_region_t<NB>(stream, 0, b1, lane, &s1d, &s1jd);
-    dense_region_t<NB>(stream, b1, jend, lane, &s2d, &s2jd);
+    if (b1 > 0) dense_region_t<NB, NT>(stream, 0, b1, lane, &s1d, &s1jd);
+    dense_region_t<NB, NT>(stream, b1, jend, lane, &s2d, &s2jd);
     // j = bidx + 1  =>  sum j*d = sum bidx*d + sum d
     uint64_t sum_jd2 = (uint64_t)s2jd + (uint64_t)s2d;
     uint64_t acc = nsel * (uint64_t)s1d;
@@ -550,8 +558,8 @@ __device__ __forceinline__ uint64_t dense_delta_weighted_t(
 __device__ uint64_t dense_delta_weighted(const uint8_t *stream,
                                          int64_t n_deltas, int64_t r0,
                                          int64_t r1, int lane) {
-    return dense_delta_weighted_t<DENSE_CHUNKS_CALL>(stream, n_deltas, r0, r1,
-                                                     lane);
+    return dense_delta_weighted_t<DENSE_CHUNKS_CALL, false>(stream, n_deltas,
+                                                            r0, r1, lane);
 }
 
 // Fast weighted delta fold: 256-byte windows (one dword per lane) with an
@@ -2904,8 +2912,11 @@ __device__ void fold_range(const uint8_t *fstream, uint8_t fenc, int64_t first,
 // host tracks the part's ts extent and selects the instantiation).  The
 // clamp's scan machinery otherwise inflates register pressure enough to
 // spill scratch reloads into the dense fold loop (~7% on the headline).
+// EN_STREAM — the closed-form instantiations only: the dense fold reads
+// its chunks with non-temporal loads (dense_region_t).  The host picks it
+// per pass from the session's stream-load policy.
 template <bool EN_VALUES, bool EN_PREDS, bool EN_GROUPS, bool EN_WALK,
-          bool EN_CLAMP>
+          bool EN_CLAMP, bool EN_STREAM = false>
 // Occupancy: 4 waves/SIMD for the value-scan instantiations — requesting
 // 6 forces scratch spills into the window loop and measured ~1.6x SLOWER.
 // Occupancy: the clamp-free value-scan instantiations (the analytic
@@ -3461,7 +3472,7 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
                         acc = !UNI_DESC
                                   ? dense_delta_weighted(fstream, n - 1, r0,
                                                          r1, lane)
-                                  : dense_delta_weighted_t<EN_CLAMP ? DENSE_CHUNKS_CLAMP : DENSE_CHUNKS_BLOCK>(
+                                  : dense_delta_weighted_t<EN_CLAMP ? DENSE_CHUNKS_CLAMP : DENSE_CHUNKS_BLOCK, EN_STREAM>(
                                         fstream, n - 1, r0, r1, lane);
                     } else {
                         acc = fold_delta_weighted_fast(fstream, n - 1, r0, r1,
@@ -3806,7 +3817,32 @@ struct bydb_session {
     float last_ms = 0.0f;
     bool consumed = false;
     int16_t float_exp = 0;  // shared decimal exponent for float64 restore
+    int stream_policy = BYDB_STREAM_AUTO;  // dense-stream load policy
 };
+
+// What a read-once pass has to exceed before its loads bypass the caches:
+// the MI355X Infinity Cache (256 MiB).  A smaller resident part is served
+// from that cache pass after pass, and non-temporal loads would turn those
+// hits into HBM reads.
+static const uint64_t STREAM_CACHE_BYTES = 256ull << 20;
+
+extern "C" int bydb_stream_policy_pick(int policy, uint64_t payload_bytes) {
+    if (policy == BYDB_STREAM_CACHED) return BYDB_STREAM_CACHED;
+    if (policy == BYDB_STREAM_STREAMING) return BYDB_STREAM_STREAMING;
+    if (policy != BYDB_STREAM_AUTO) return BYDB_ERR_BAD_ARG;
+    return payload_bytes > STREAM_CACHE_BYTES ? BYDB_STREAM_STREAMING
+                                              : BYDB_STREAM_CACHED;
+}
+
+extern "C" int bydb_set_stream_policy(bydb_session *s, int policy) {
+    if (policy != BYDB_STREAM_AUTO && policy != BYDB_STREAM_CACHED &&
+        policy != BYDB_STREAM_STREAMING) {
+        s->err = "unknown stream policy";
+        return BYDB_ERR_BAD_ARG;
+    }
+    s->stream_policy = policy;
+    return BYDB_OK;
+}
 
 #define HIP_TRY(s, call)                                                      \
     do {                                                                      \
@@ -4350,6 +4386,14 @@ static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
         BYDB_KSEL(false)
     }
 #undef BYDB_KSEL
+    // the closed-form scan of a part too large for the last-level cache
+    // (or a forced policy) reads its dense streams past the caches
+    if (!en_values && !en_preds && !en_groups &&
+        bydb_stream_policy_pick(s->stream_policy, s->payload_len) ==
+            BYDB_STREAM_STREAMING)
+        kfn = en_clamp
+                  ? k_scan_agg_t<false, false, false, false, true, true>
+                  : k_scan_agg_t<false, false, false, false, false, true>;
     // light pass: every block whose predicate verdict is uniform (no
     // walker state, no scratch spills in the scan loop)
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(threads), 0, s->stream,

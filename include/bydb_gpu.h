@@ -349,6 +349,26 @@ int bydb_reduce_partials2(const bydb_partial *parts, int64_t n_parts_per_group,
                           int64_t n_groups, int field_vtype, int16_t float_exp,
                           bydb_result *out);
 
+/* How the closed-form scan (sum/count, no predicate, no tag group-by) loads
+ * the dense one-byte delta streams.  CACHED: plain loads, every line is
+ * installed in the caches — right for a part small enough to stay resident
+ * in the last-level cache between passes.  STREAMING: non-temporal loads —
+ * right for a read-once pass over a part larger than that cache.  AUTO (the
+ * default) picks STREAMING when the resident payload exceeds the cache
+ * (256 MiB), CACHED otherwise.  Results do not depend on the policy.
+ * BYDB_ERR_BAD_ARG (session stays usable) for any other value. */
+enum {
+    BYDB_STREAM_AUTO = 0,
+    BYDB_STREAM_CACHED = 1,
+    BYDB_STREAM_STREAMING = 2,
+};
+int bydb_set_stream_policy(bydb_session *s, int policy);
+
+/* What `policy` resolves to for a resident payload of payload_bytes:
+ * BYDB_STREAM_CACHED or BYDB_STREAM_STREAMING (host-only, no session), or
+ * BYDB_ERR_BAD_ARG for an unknown policy. */
+int bydb_stream_policy_pick(int policy, uint64_t payload_bytes);
+
 /* Timing of the last consume's kernels in milliseconds (HIP events on the
  * session stream) — feeds bench.py's roofline.achieved. */
 double bydb_last_consume_ms(bydb_session *s);
