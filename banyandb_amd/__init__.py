@@ -222,6 +222,27 @@ def filter_nodes_table(nodes, n_conds):
     return sum(int(out[w]) << (64 * w) for w in range(4))
 
 
+def row_dedup_peers(descs):
+    """The overlap planner of the cross-part version dedup over a list of
+    BlockDesc (only series_id, ts_min and ts_max are read): per block the
+    ascending list of blocks of the same series whose [ts_min, ts_max]
+    intersects its own.  Pure host."""
+    n = len(descs)
+    arr = (BlockDesc * max(n, 1))(*descs)
+    offs = (C.c_uint64 * (n + 1))()
+    need = C.c_uint64(0)
+    rc = _lib.bydb_row_dedup_peers(arr, n, offs, None, 0, C.byref(need))
+    if rc not in (0, -7):
+        raise ValueError(f"bydb_row_dedup_peers rc={rc}")
+    peers = (C.c_uint32 * max(need.value, 1))()
+    rc = _lib.bydb_row_dedup_peers(arr, n, offs, peers, need.value,
+                                   C.byref(need))
+    if rc != 0:
+        raise ValueError(f"bydb_row_dedup_peers rc={rc}")
+    return [[int(peers[k]) for k in range(offs[i], offs[i + 1])]
+            for i in range(n)]
+
+
 def _build_if_possible():
     from banyandb_amd.build import build
     return build(verbose=False)
@@ -260,6 +281,8 @@ def _load():
     lib.bydb_part_reserve.argtypes = [C.c_void_p, C.c_uint64, C.c_int64]
     lib.bydb_part_append.restype = C.c_int
     lib.bydb_part_append.argtypes = [C.c_void_p, u8p, C.c_uint64, bp, C.c_int64]
+    lib.bydb_part_clear.restype = C.c_int
+    lib.bydb_part_clear.argtypes = [C.c_void_p]
     lib.bydb_agg_configure.restype = C.c_int
     lib.bydb_agg_configure.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_int]
     lib.bydb_agg_configure_by_tags.restype = C.c_int
@@ -295,6 +318,15 @@ def _load():
                                            C.c_int, C.POINTER(C.c_uint64)]
     lib.bydb_filter_tree_stats.restype = C.c_int
     lib.bydb_filter_tree_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.bydb_set_row_dedup.restype = C.c_int
+    lib.bydb_set_row_dedup.argtypes = [C.c_void_p, C.c_int]
+    lib.bydb_row_dedup_stats.restype = C.c_int
+    lib.bydb_row_dedup_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.bydb_row_dedup_peers.restype = C.c_int
+    lib.bydb_row_dedup_peers.argtypes = [bp, C.c_int64,
+                                         C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint32), C.c_uint64,
+                                         C.POINTER(C.c_uint64)]
     lib.bydb_finalize.restype = C.c_int
     lib.bydb_finalize.argtypes = [C.c_void_p, C.POINTER(Result), C.c_int64]
     lib.bydb_finalize_partials.restype = C.c_int
@@ -557,6 +589,10 @@ class Session:
                                        builder.payload_len, builder.blocks_ptr(),
                                        builder.n_blocks))
 
+    def clear_part(self):
+        """Drop the resident part (the reservation is kept)."""
+        self._ck(_lib.bydb_part_clear(self._h))
+
     def configure(self, field_vtype, funcs, n_groups=1, mode=MODE_ALL,
                   float_exp=0):
         mask = 0
@@ -659,6 +695,22 @@ class Session:
         code-mask walk, row-bitmap walk]; zeros when the tree had no OR."""
         out = (C.c_uint64 * 4)()
         self._ck(_lib.bydb_filter_tree_stats(self._h, out))
+        return [int(x) for x in out]
+
+    def set_row_dedup(self, on):
+        """Cross-part version dedup (the measure query's merge,
+        banyand/measure/query.go:913-943, 966-1026): with on=1 a row is
+        dropped when another resident row of its series and timestamp has
+        a greater version, or an equal version and an earlier block.
+        Sticky; off by default."""
+        self._ck(_lib.bydb_set_row_dedup(self._h, int(on)))
+
+    def row_dedup_stats(self):
+        """[overlapping blocks, partially superseded blocks, fully
+        superseded blocks, superseded rows] of the resident part; zeros
+        before the first consume with dedup on and whenever it is off."""
+        out = (C.c_uint64 * 4)()
+        self._ck(_lib.bydb_row_dedup_stats(self._h, out))
         return [int(x) for x in out]
 
     def finalize(self):

@@ -36,6 +36,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -3733,6 +3734,438 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
                   first_seen, wfirst);
 }
 
+// ---------------- cross-part version dedup ----------------
+// The reference's measure query merges the block cursors of every part
+// through a heap: for equal (seriesID, timestamp) queryResult.Less orders
+// versions descending and queryResult.merge keeps the first row, replacing
+// it only by a later row of greater version (banyand/measure/
+// query.go:913-943, 966-1026).  Exactly one row per (series, timestamp)
+// survives: the one with the highest version.  The order of equal versions
+// is arbitrary there (heap order of equal keys); here the row of the
+// EARLIEST APPENDED block wins.
+//
+// Which rows survive depends on the resident part only, so it is computed
+// once per part (dedup_build): the host plans which blocks overlap
+// (bydb_row_dedup_peers), k_dedup_decode materialises the stream-coded
+// timestamps / versions of those blocks, k_dedup_mark writes a survivor
+// bitmap per block.  Per consume k_dedup_apply folds the bitmaps into the
+// verdicts, masks and bitmaps the resolve stage wrote, so the scan kernel
+// sees nothing new: a fully superseded block is PF_SKIP, a partially
+// superseded one a row-bitmap predicate on slot 0.
+#define DD_TS_CONST 0    // every row at ts_min
+#define DD_TS_ARITH 1    // ts_min + row * dd (DeltaConst)
+#define DD_TS_ARENA 2    // decoded rows in the arena
+#define DD_NO_ARENA (~0ull)
+
+// One block that overlaps another block of its series ("involved").
+struct DedupInfo {
+    uint32_t block;       // block index in append order
+    uint32_t count;
+    int64_t ts_min, ts_max;
+    int64_t dd;           // DD_TS_ARITH stride (written by k_dedup_decode)
+    int64_t ver_first;
+    uint64_t ts_arena;    // first arena row of the timestamps (DD_TS_ARENA)
+    uint64_t ver_arena;   // first arena row of the versions, DD_NO_ARENA
+                          // when the version is Const (= ver_first)
+    uint32_t ts_kind;     // DD_TS_*
+    uint32_t _p;
+};
+
+// counters of the mark stage
+#define DD_CTR_PARTIAL 1
+#define DD_CTR_FULL 2
+#define DD_CTR_ROWS 3
+
+// Decode a delta / delta-of-delta varint stream into out[row] — the window
+// walk of clamp_count_stream, storing every value instead of counting.
+// Rows 0 (and 1 for dod) are the caller's.  Every 64-byte window is checked
+// against `avail`, the bytes readable from `stream` on; asc: a negative
+// step is a descending timestamp list (the reference never writes one).
+__device__ void dedup_decode_stream(const uint8_t *stream, uint64_t avail,
+                                    int64_t n_deltas, bool dod,
+                                    int64_t first_plus, int64_t d1_init,
+                                    bool asc, int lane, int64_t *out,
+                                    DevErr *derr, uint64_t bi) {
+    uint64_t pos = 0;
+    int64_t j = dod ? 2 : 1;
+    int64_t jmax = n_deltas;
+    uint64_t v_carry = (uint64_t)first_plus;
+    uint64_t d1_carry = (uint64_t)d1_init;
+    uint64_t carry_u = 0;
+    uint32_t carry_n = 0;
+    while (j <= jmax) {
+        if (pos + 64 > avail) { dev_set_err(derr, DERR_BAD_STREAM, bi); break; }
+        uint8_t b = stream[pos + (uint64_t)lane];
+        uint64_t emask = __ballot(b < 0x80);
+        if (emask == 0) { dev_set_err(derr, DERR_BAD_STREAM, bi); break; }
+        int rank = __popcll(emask & lanemask_lt(lane));
+        int64_t myj = j + rank;
+        bool is_term = (b < 0x80) && (myj <= jmax);
+        int nterm = __popcll(emask);
+        uint64_t d = 0;
+        if (emask == ~0ull && carry_n == 0) {
+            d = (uint64_t)zz_dec(b);
+        } else {
+            uint64_t below = emask & lanemask_lt(lane);
+            int start = below ? (64 - __clzll(below)) : 0;
+            int mylen = lane - start + 1;
+            if (mylen > 10) mylen = 10;
+            int maxlen = (b < 0x80) ? mylen : 1;
+            for (int off2 = 32; off2 > 0; off2 >>= 1) {
+                int t = __shfl_xor(maxlen, off2);
+                maxlen = t > maxlen ? t : maxlen;
+            }
+            uint64_t u = (uint64_t)(b & 0x7f) << (7 * (mylen - 1));
+            for (int k = 1; k < maxlen; ++k) {
+                uint32_t bk = (uint32_t)__shfl_up((int)b, k);
+                if (k < mylen)
+                    u |= (uint64_t)(bk & 0x7f) << (7 * (mylen - 1 - k));
+            }
+            if (below == 0 && carry_n)
+                u = carry_u | (u << (7 * carry_n));
+            if (is_term) d = (uint64_t)zz_dec(u);
+        }
+        if (!is_term) d = 0;
+        uint64_t val;
+        bool desc;
+        if (dod) {
+            uint64_t s1 = wave_incl_scan(d, lane);
+            uint64_t d1j = is_term ? (d1_carry + s1) : 0;
+            uint64_t s2 = wave_incl_scan(d1j, lane);
+            val = v_carry + s2;
+            v_carry += readlane64(s2, 63);
+            d1_carry += readlane64(s1, 63);
+            desc = (int64_t)d1j < 0;
+        } else {
+            uint64_t sscan = wave_incl_scan(d, lane);
+            val = v_carry + sscan;
+            v_carry += readlane64(sscan, 63);
+            desc = (int64_t)d < 0;
+        }
+        if (asc && __any(is_term && desc)) {
+            dev_set_err(derr, DERR_DESC_TS, bi);
+            break;
+        }
+        if (is_term) out[myj] = (int64_t)val;
+        if (j + nterm > jmax) break;
+        int last_lane = 63 - __clzll(emask);
+        int n_tail = 63 - last_lane;
+        if (n_tail) {
+            uint64_t tail = 0;
+            if (lane > last_lane) {
+                int sh2 = lane - last_lane - 1;
+                if (sh2 > 9) sh2 = 9;
+                tail = (uint64_t)(b & 0x7f) << (7 * sh2);
+            }
+            for (int off2 = 32; off2 > 0; off2 >>= 1)
+                tail |= (uint64_t)__shfl_xor((long long)tail, off2);
+            carry_u = tail;
+            carry_n = n_tail > 9 ? 9 : (uint32_t)n_tail;
+        } else {
+            carry_u = 0;
+            carry_n = 0;
+        }
+        j += nterm;
+        pos += 64;
+    }
+}
+
+// One int64 list of `n` values (first value `first`, stream at payload +
+// off) decoded into out[0..n).  DeltaConst lists are expanded, Const lists
+// never get here.
+__device__ void dedup_decode_list(const uint8_t *payload, uint64_t off,
+                                  uint64_t limit, uint8_t enc, int64_t first,
+                                  int64_t n, bool asc, int lane, int64_t *out,
+                                  DevErr *derr, uint64_t bi) {
+    if (off + 11 > limit) { dev_set_err(derr, DERR_BAD_STREAM, bi); return; }
+    const uint8_t *s = payload + off;
+    if (lane == 0) out[0] = first;
+    if (n < 2) return;
+    if (enc == BYDB_ENC_DELTA_CONST) {
+        int vl;
+        int64_t dd = decode_one_varint(s, &vl);
+        for (int64_t i = 1 + lane; i < n; i += WAVE)
+            out[i] = (int64_t)((uint64_t)first + (uint64_t)i * (uint64_t)dd);
+        return;
+    }
+    const bool dod = enc == BYDB_ENC_DELTA_OF_DELTA;
+    int64_t d1 = 0, first_plus = first;
+    if (dod) {
+        int vl;
+        d1 = decode_one_varint(s, &vl);
+        s += vl;
+        off += (uint64_t)vl;
+        first_plus = (int64_t)((uint64_t)first + (uint64_t)d1);
+        if (asc && d1 < 0) { dev_set_err(derr, DERR_DESC_TS, bi); return; }
+        if (lane == 0) out[1] = first_plus;
+    }
+    dedup_decode_stream(s, limit - off, n - 1, dod, first_plus, d1, asc, lane,
+                        out, derr, bi);
+}
+
+// One wave per involved block: timestamps coded Delta / DeltaOfDelta and
+// versions coded anything but Const are decoded into the arena (16 B per
+// row when both are); Const / DeltaConst timestamps stay closed form and
+// only leave their stride in the block's DedupInfo.  The version list
+// follows the timestamp list in the block's timestamps payload
+// (block.go:386-404): it starts at ts_off + ts_len and its length is not in
+// the descriptor, so every read is bounded by `limit`, the end of the
+// payload arena's readable bytes.
+__global__ __launch_bounds__(WAVE) void k_dedup_decode(
+    const uint8_t *__restrict__ payload, uint64_t limit,
+    const bydb_block_desc *__restrict__ blocks, DedupInfo *__restrict__ infos,
+    int64_t n_inv, int64_t *__restrict__ arena, DevErr *derr) {
+    const int lane = threadIdx.x;
+    for (int64_t ia = blockIdx.x; ia < n_inv; ia += gridDim.x) {
+        const DedupInfo in = infos[ia];
+        const bydb_block_desc *bd = &blocks[in.block];
+        const int64_t n = (int64_t)in.count;
+        if (in.ts_min > in.ts_max) {
+            dev_set_err(derr, DERR_DESC_TS, (uint64_t)in.block);
+            continue;
+        }
+        if (in.ts_kind == DD_TS_ARITH) {
+            if (bd->ts_off + 11 > limit) {
+                dev_set_err(derr, DERR_BAD_STREAM, (uint64_t)in.block);
+                continue;
+            }
+            int vl;
+            int64_t dd = decode_one_varint(payload + bd->ts_off, &vl);
+            if (dd <= 0)
+                dev_set_err(derr, DERR_DESC_TS, (uint64_t)in.block);
+            if (lane == 0) infos[ia].dd = dd;
+        } else if (in.ts_kind == DD_TS_ARENA) {
+            uint8_t tenc = bd->ts_enc_with_version;
+            uint8_t tc = tenc >= BYDB_ENC_CONST_WV ? tenc - 4 : tenc;
+            dedup_decode_list(payload, bd->ts_off, limit, tc, in.ts_min, n,
+                              true, lane, arena + in.ts_arena, derr,
+                              (uint64_t)in.block);
+        }
+        if (in.ver_arena != DD_NO_ARENA)
+            dedup_decode_list(payload, bd->ts_off + bd->ts_len, limit,
+                              bd->version_enc, in.ver_first, n, false, lane,
+                              arena + in.ver_arena, derr, (uint64_t)in.block);
+    }
+}
+
+__device__ __forceinline__ int64_t dd_ts_of(const DedupInfo &in,
+                                            const int64_t *arena, int64_t row) {
+    if (in.ts_kind == DD_TS_ARENA) return arena[in.ts_arena + (uint64_t)row];
+    return (int64_t)((uint64_t)in.ts_min + (uint64_t)row * (uint64_t)in.dd);
+}
+
+__device__ __forceinline__ int64_t dd_ver_of(const DedupInfo &in,
+                                             const int64_t *arena,
+                                             int64_t row) {
+    if (in.ver_arena == DD_NO_ARENA) return in.ver_first;
+    return arena[in.ver_arena + (uint64_t)row];
+}
+
+// Rows [*lo, *hi) of block `in` whose timestamp equals ts (ts lies inside
+// the block's range).  Timestamps inside a block ascend; equal neighbours
+// are tolerated by returning the whole equal run.
+__device__ __forceinline__ void dd_find_ts(const DedupInfo &in,
+                                           const int64_t *arena, int64_t ts,
+                                           int64_t *lo, int64_t *hi) {
+    *lo = 0;
+    *hi = 0;
+    if (in.ts_kind == DD_TS_CONST) {
+        if (ts == in.ts_min) *hi = (int64_t)in.count;
+        return;
+    }
+    if (in.ts_kind == DD_TS_ARITH) {
+        if (in.dd <= 0) return;
+        uint64_t off = (uint64_t)ts - (uint64_t)in.ts_min;
+        uint64_t row = off / (uint64_t)in.dd;
+        if (row * (uint64_t)in.dd == off && row < in.count) {
+            *lo = (int64_t)row;
+            *hi = (int64_t)row + 1;
+        }
+        return;
+    }
+    const int64_t *t = arena + in.ts_arena;
+    int64_t a = 0, b = (int64_t)in.count;
+    while (a < b) {               // first row with t[row] >= ts
+        int64_t m = (a + b) >> 1;
+        if (t[m] < ts) a = m + 1;
+        else b = m;
+    }
+    int64_t e = a;
+    while (e < (int64_t)in.count && t[e] == ts) e++;
+    *lo = a;
+    *hi = e;
+}
+
+// One wave per involved block A: a survivor bit per row.  A row is
+// superseded when a peer block holds a row of the same timestamp with a
+// greater version, or with an equal version and a smaller block index.
+// 64 rows per step, one ballot word per step; a peer whose range misses the
+// step's rows costs one compare.  The block is then classified: nothing
+// dropped (untouched), everything dropped (listed in flist), or partial
+// (listed in plist, its 128-word bitmap kept in the survivor arena at the
+// list position).
+__global__ __launch_bounds__(WAVE) void k_dedup_mark(
+    const DedupInfo *__restrict__ infos, int64_t n_inv,
+    const uint64_t *__restrict__ peer_offs, const uint32_t *__restrict__ peers,
+    const int64_t *__restrict__ arena, uint64_t *__restrict__ surv,
+    uint32_t *__restrict__ plist, uint32_t *__restrict__ flist,
+    unsigned long long *__restrict__ ctr) {
+    const int lane = threadIdx.x;
+    for (int64_t ia = blockIdx.x; ia < n_inv; ia += gridDim.x) {
+        const DedupInfo A = infos[ia];
+        const int64_t n = (int64_t)A.count;
+        const uint64_t p0 = peer_offs[ia], p1 = peer_offs[ia + 1];
+        uint64_t w0 = 0, w1 = 0;     // words lane, lane + 64 of the bitmap
+        uint64_t dropped = 0;
+        for (int64_t base = 0; base < n; base += WAVE) {
+            const int64_t row = base + lane;
+            const bool valid = row < n;
+            const int nvalid = (int)(n - base < WAVE ? n - base : WAVE);
+            const int64_t ts = valid ? dd_ts_of(A, arena, row) : 0;
+            const int64_t ver = valid ? dd_ver_of(A, arena, row) : 0;
+            const int64_t c_lo = (int64_t)readlane64((uint64_t)ts, 0);
+            const int64_t c_hi = (int64_t)__shfl((long long)ts, nvalid - 1);
+            bool sup = false;
+            for (uint64_t p = p0; p < p1; p++) {
+                const DedupInfo B = infos[peers[p]];
+                if (B.ts_max < c_lo || B.ts_min > c_hi) continue;
+                if (valid && !sup && ts >= B.ts_min && ts <= B.ts_max) {
+                    int64_t lo, hi;
+                    dd_find_ts(B, arena, ts, &lo, &hi);
+                    for (int64_t r = lo; r < hi && !sup; r++) {
+                        int64_t vb = dd_ver_of(B, arena, r);
+                        sup = vb > ver || (vb == ver && B.block < A.block);
+                    }
+                }
+            }
+            const uint64_t word = __ballot(valid && !sup);
+            dropped += (uint64_t)(nvalid - __popcll(word));
+            const int c = (int)(base >> 6);
+            if (lane == (c & 63)) {
+                if (c < 64) w0 = word;
+                else w1 = word;
+            }
+        }
+        if (dropped == 0) continue;
+        unsigned long long k = 0;
+        if (lane == 0) {
+            k = atomicAdd(&ctr[dropped == (uint64_t)n ? DD_CTR_FULL
+                                                      : DD_CTR_PARTIAL], 1ull);
+            atomicAdd(&ctr[DD_CTR_ROWS], (unsigned long long)dropped);
+        }
+        k = readlane64(k, 0);
+        if (dropped == (uint64_t)n) {
+            if (lane == 0) flist[k] = A.block;
+        } else {
+            if (lane == 0) plist[k] = A.block;
+            surv[k * PLAIN_BM_WORDS + (uint64_t)lane] = w0;
+            surv[k * PLAIN_BM_WORDS + 64 + (uint64_t)lane] = w1;
+        }
+    }
+}
+
+// Per consume: fold the survivors into what the resolve stage wrote (or
+// into an all-CLEAR flag table for an unfiltered consume, n_slots == 0).
+// One thread per fully superseded block flags it PF_SKIP.  One wave per
+// partially superseded block, unless its verdict is SKIP or ERR already:
+// the block becomes PF_WALK with slot 0 a row-bitmap predicate and the
+// other slots disabled; its bitmap, in the pred_bm arena from word bm_base
+// on, is survivors & rows(slot 0) & rows(slot 1) & rows(slot 2), where
+// rows(slot) is all ones for a disabled / CLEAR slot, the code mask
+// expanded per row through the RLE cursor for a dictionary slot, and the
+// existing bitmap for a plain or tree row-bitmap slot.  The walk census
+// follows, so the heavy pass still exits early when nothing walks.
+__global__ __launch_bounds__(WAVE) void k_dedup_apply(
+    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
+    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
+    const uint32_t *__restrict__ plist, int64_t n_partial,
+    const uint32_t *__restrict__ flist, int64_t n_full,
+    const uint64_t *__restrict__ surv, PredBlock *preds, int n_slots,
+    uint8_t *flags, uint64_t *pred_bm, uint64_t bm_base,
+    uint32_t *walk_count) {
+    const int lane = threadIdx.x;
+    for (int64_t t = (int64_t)blockIdx.x * WAVE + lane; t < n_full;
+         t += (int64_t)gridDim.x * WAVE) {
+        const uint32_t bi = flist[t];
+        if (flags[bi] == PF_WALK) atomicSub(walk_count, 1u);
+        flags[bi] = PF_SKIP;
+    }
+    for (int64_t p = blockIdx.x; p < n_partial; p += gridDim.x) {
+        const int64_t bi = (int64_t)plist[p];
+        const uint8_t f = flags[bi];
+        if (f == PF_SKIP || f == PF_ERR) continue;
+        const int64_t n = (int64_t)blocks[bi].count;
+        // per slot: 0 = no constraint, 1 = no row, 2 = bitmap, 3 = RLE mask
+        int kind[3] = {0, 0, 0};
+        uint64_t bm_off[3] = {0, 0, 0};
+        uint64_t mask[3][4];
+        CodeWalk cw[3];
+#pragma unroll
+        for (int sl = 0; sl < 3; sl++) {
+            if (f != PF_WALK || sl >= n_slots) continue;
+            const PredBlock pb = preds[(int64_t)sl * n_blocks + bi];
+            if (pb.disabled) continue;
+            if (!pb.active) { kind[sl] = 1; continue; }
+            if (pb.plain) {
+                kind[sl] = 2;
+                bm_off[sl] = pb.rle_bit_off;
+                continue;
+            }
+            kind[sl] = 3;
+#pragma unroll
+            for (int i = 0; i < 4; i++) mask[sl][i] = pb.mask[i];
+            cw[sl].base = (pb.rle_bit_off & TAG_SIDECAR_BIT) ? sidecar
+                                                             : payload;
+            cw[sl].bit0 = pb.rle_bit_off & ~TAG_SIDECAR_BIT;
+            cw[sl].nentries = pb.nentries;
+            cw[sl].width = pb.width;
+            cw[sl].entry = 0;
+            cw[sl].run_lo = 0;
+            cw[sl].run_hi = 0;
+            cw[sl].run_code = CODE_NONE;
+        }
+        const uint64_t out0 = bm_base + (uint64_t)p * PLAIN_BM_WORDS;
+        for (int64_t base = 0; base < n; base += WAVE) {
+            const int64_t row = base + lane;
+            const bool valid = row < n;
+            const uint64_t c = (uint64_t)(base >> 6);
+            uint64_t word = surv[(uint64_t)p * PLAIN_BM_WORDS + c];
+#pragma unroll
+            for (int sl = 0; sl < 3; sl++) {
+                if (kind[sl] == 1) {
+                    word = 0;
+                } else if (kind[sl] == 2) {
+                    word &= pred_bm[bm_off[sl] + c];
+                } else if (kind[sl] == 3) {
+                    uint32_t code = code_of_rows(&cw[sl], row, valid);
+                    uint32_t w = (code >> 6) & 3;
+                    uint64_t m = w == 0 ? mask[sl][0] : w == 1 ? mask[sl][1]
+                                 : w == 2 ? mask[sl][2] : mask[sl][3];
+                    word &= __ballot(valid && code != CODE_NONE &&
+                                     ((m >> (code & 63)) & 1));
+                }
+            }
+            if (lane == 0) pred_bm[out0 + c] = word;
+        }
+        if (lane == 0) {
+            PredBlock pb;
+            for (int i = 0; i < 4; i++) pb.mask[i] = 0;
+            pb.rle_bit_off = 0; pb.nentries = 0; pb.width = 0;
+            pb.active = 0; pb.err = 0; pb.uniform = 0; pb.plain = 0;
+            pb.disabled = 1;
+            for (int sl = 1; sl < n_slots; sl++)
+                preds[(int64_t)sl * n_blocks + bi] = pb;
+            pb.rle_bit_off = out0;
+            pb.active = 1;
+            pb.plain = 1;
+            pb.disabled = 0;
+            preds[bi] = pb;
+            flags[bi] = PF_WALK;
+            if (f == PF_CLEAR) atomicAdd(walk_count, 1u);
+        }
+    }
+}
+
 // init kernel: set partials to the fold identity (Map.Reset, function.go)
 __global__ void k_reset_partials(bydb_partial *p, int64_t n) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3818,6 +4251,20 @@ struct bydb_session {
     bool consumed = false;
     int16_t float_exp = 0;  // shared decimal exponent for float64 restore
     int stream_policy = BYDB_STREAM_AUTO;  // dense-stream load policy
+    // cross-part version dedup (bydb_set_row_dedup): derived state over
+    // the resident part, built on the first consume with dedup on
+    int row_dedup = 0;
+    bool dedup_built = false;
+    uint64_t dedup_stats[4] = {0, 0, 0, 0};
+    int64_t dd_n_inv = 0, dd_n_partial = 0, dd_n_full = 0;
+    DedupInfo *d_dd_infos = nullptr;
+    uint64_t *d_dd_peer_offs = nullptr;
+    uint32_t *d_dd_peers = nullptr;
+    int64_t *d_dd_arena = nullptr;
+    uint64_t *d_dd_surv = nullptr;
+    uint32_t *d_dd_plist = nullptr, *d_dd_flist = nullptr;
+    unsigned long long *d_dd_ctr = nullptr;
+    uint64_t dd_bm_base = 0;   // first pred_bm word of the merged bitmaps
 };
 
 // What a read-once pass has to exceed before its loads bypass the caches:
@@ -3852,6 +4299,21 @@ extern "C" int bydb_set_stream_policy(bydb_session *s, int policy) {
             return BYDB_ERR_HIP;                                              \
         }                                                                     \
     } while (0)
+
+static void dedup_free(bydb_session *s) {
+    if (s->d_dd_infos) (void)hipFree(s->d_dd_infos);
+    if (s->d_dd_peer_offs) (void)hipFree(s->d_dd_peer_offs);
+    if (s->d_dd_peers) (void)hipFree(s->d_dd_peers);
+    if (s->d_dd_arena) (void)hipFree(s->d_dd_arena);
+    if (s->d_dd_surv) (void)hipFree(s->d_dd_surv);
+    if (s->d_dd_plist) (void)hipFree(s->d_dd_plist);
+    if (s->d_dd_flist) (void)hipFree(s->d_dd_flist);
+    if (s->d_dd_ctr) (void)hipFree(s->d_dd_ctr);
+    s->d_dd_infos = nullptr; s->d_dd_peer_offs = nullptr;
+    s->d_dd_peers = nullptr; s->d_dd_arena = nullptr;
+    s->d_dd_surv = nullptr; s->d_dd_plist = nullptr;
+    s->d_dd_flist = nullptr; s->d_dd_ctr = nullptr;
+}
 
 extern "C" bydb_session *bydb_session_create(int device) {
     int n = 0;
@@ -3908,6 +4370,7 @@ extern "C" void bydb_session_destroy(bydb_session *s) {
     if (s->d_walk_count) (void)hipFree(s->d_walk_count);
     if (s->d_tree_stats) (void)hipFree(s->d_tree_stats);
     if (s->d_first_seen) (void)hipFree(s->d_first_seen);
+    dedup_free(s);
     if (s->ev_start) (void)hipEventDestroy(s->ev_start);
     if (s->ev_stop) (void)hipEventDestroy(s->ev_stop);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -3939,6 +4402,7 @@ extern "C" int bydb_part_reserve(bydb_session *s, uint64_t payload_bytes,
     s->n_plain_host = 0;
     s->segs_built = false;
     s->groups_built = false;
+    s->dedup_built = false;
     return BYDB_OK;
 }
 
@@ -3948,6 +4412,7 @@ extern "C" int bydb_part_append(bydb_session *s, const uint8_t *payload,
     HIP_TRY(s, hipSetDevice(s->device));
     s->segs_built = false;
     s->groups_built = false;
+    s->dedup_built = false;
     if (s->payload_len + len > s->payload_cap ||
         s->n_blocks + n_blocks > s->blocks_cap) {
         s->err = "part_append exceeds reservation";
@@ -4422,6 +4887,289 @@ static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
     return BYDB_OK;
 }
 
+// ---- cross-part version dedup: planner, build, per-consume apply ----
+// (header: "cross-part version dedup"; kernels: k_dedup_decode / _mark /
+// _apply)
+
+// The overlap planner.  Block indices sorted by (series_id, ts_min); inside
+// one series a block's peers among the later ones are exactly those whose
+// ts_min does not exceed its ts_max, so the sweep stops at the first that
+// does.  Output: symmetric CSR, each list ascending by block index.
+static void plan_peers(const bydb_block_desc *blocks, int64_t n,
+                       std::vector<uint64_t> &offs,
+                       std::vector<uint32_t> &peers) {
+    std::vector<uint32_t> ord((size_t)n);
+    for (int64_t i = 0; i < n; i++) ord[(size_t)i] = (uint32_t)i;
+    std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) {
+        if (blocks[a].series_id != blocks[b].series_id)
+            return blocks[a].series_id < blocks[b].series_id;
+        if (blocks[a].ts_min != blocks[b].ts_min)
+            return blocks[a].ts_min < blocks[b].ts_min;
+        return a < b;
+    });
+    offs.assign((size_t)n + 1, 0);
+    for (int pass = 0; pass < 2; pass++) {
+        std::vector<uint64_t> fill;
+        if (pass == 1) {
+            for (int64_t i = 0; i < n; i++) offs[(size_t)i + 1] += offs[(size_t)i];
+            peers.assign((size_t)offs[(size_t)n], 0);
+            fill.assign(offs.begin(), offs.end() - 1);
+        }
+        for (int64_t i = 0; i < n; i++) {
+            const bydb_block_desc &a = blocks[ord[(size_t)i]];
+            for (int64_t j = i + 1; j < n; j++) {
+                const bydb_block_desc &b = blocks[ord[(size_t)j]];
+                if (b.series_id != a.series_id || b.ts_min > a.ts_max) break;
+                if (pass == 0) {
+                    offs[(size_t)ord[(size_t)i] + 1]++;
+                    offs[(size_t)ord[(size_t)j] + 1]++;
+                } else {
+                    peers[(size_t)fill[ord[(size_t)i]]++] = ord[(size_t)j];
+                    peers[(size_t)fill[ord[(size_t)j]]++] = ord[(size_t)i];
+                }
+            }
+        }
+    }
+    for (int64_t i = 0; i < n; i++)
+        std::sort(peers.begin() + (ptrdiff_t)offs[(size_t)i],
+                  peers.begin() + (ptrdiff_t)offs[(size_t)i + 1]);
+}
+
+extern "C" int bydb_row_dedup_peers(const bydb_block_desc *blocks,
+                                    int64_t n_blocks, uint64_t *peer_offs,
+                                    uint32_t *peers, uint64_t peers_cap,
+                                    uint64_t *n_peers) {
+    if (n_blocks < 0 || n_blocks > (int64_t)UINT32_MAX ||
+        (n_blocks > 0 && blocks == nullptr) || peer_offs == nullptr ||
+        n_peers == nullptr)
+        return BYDB_ERR_BAD_ARG;
+    std::vector<uint64_t> offs;
+    std::vector<uint32_t> pl;
+    plan_peers(blocks, n_blocks, offs, pl);
+    *n_peers = pl.size();
+    memcpy(peer_offs, offs.data(), sizeof(uint64_t) * offs.size());
+    if (pl.size() > peers_cap || (!pl.empty() && peers == nullptr))
+        return BYDB_ERR_OOM;
+    if (!pl.empty()) memcpy(peers, pl.data(), sizeof(uint32_t) * pl.size());
+    return BYDB_OK;
+}
+
+extern "C" int bydb_set_row_dedup(bydb_session *s, int on) {
+    if (on != 0 && on != 1) {
+        s->err = "row dedup must be 0 or 1";
+        return BYDB_ERR_BAD_ARG;
+    }
+    s->row_dedup = on;
+    return BYDB_OK;
+}
+
+extern "C" int bydb_row_dedup_stats(bydb_session *s, uint64_t out[4]) {
+    const bool live = s->row_dedup && s->dedup_built;
+    for (int i = 0; i < 4; i++) out[i] = live ? s->dedup_stats[i] : 0;
+    return BYDB_OK;
+}
+
+// Device allocation of the dedup build: a failure is BYDB_ERR_OOM with the
+// size in the message, and turns dedup off so the session stays usable.
+template <typename T>
+static int dedup_alloc(bydb_session *s, T **p, uint64_t count,
+                       const char *what) {
+    const uint64_t bytes = (count ? count : 1) * sizeof(T);
+    if (hipMalloc(p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        char buf[160];
+        snprintf(buf, sizeof buf,
+                 "row dedup: cannot allocate %llu bytes for the %s; "
+                 "row dedup is now off",
+                 (unsigned long long)bytes, what);
+        s->err = buf;
+        dedup_free(s);
+        s->row_dedup = 0;
+        return BYDB_ERR_OOM;
+    }
+    return BYDB_OK;
+}
+
+// Once per resident part, on the first consume with dedup on: read the
+// descriptors back, plan the peers, decode and mark on the device, and
+// read the four counters back — the build's single host wait.  A part
+// without overlapping blocks allocates nothing.
+static int dedup_build(bydb_session *s) {
+    if (!s->row_dedup || s->dedup_built) return BYDB_OK;
+    dedup_free(s);
+    for (int i = 0; i < 4; i++) s->dedup_stats[i] = 0;
+    s->dd_n_inv = s->dd_n_partial = s->dd_n_full = 0;
+    const int64_t nb = s->n_blocks;
+    std::vector<bydb_block_desc> hb((size_t)nb);
+    HIP_TRY(s, hipMemcpy(hb.data(), s->d_blocks,
+                         sizeof(bydb_block_desc) * (size_t)nb,
+                         hipMemcpyDeviceToHost));
+    std::vector<uint64_t> offs;
+    std::vector<uint32_t> pl;
+    plan_peers(hb.data(), nb, offs, pl);
+    if (pl.empty()) {
+        s->dedup_built = true;
+        return BYDB_OK;
+    }
+    // involved blocks, their arena rows, and the CSR over involved indices
+    std::vector<uint32_t> inv_of((size_t)nb, 0);
+    std::vector<DedupInfo> infos;
+    std::vector<uint64_t> ioffs(1, 0);
+    uint64_t arena_rows = 0;
+    for (int64_t bi = 0; bi < nb; bi++) {
+        if (offs[(size_t)bi] == offs[(size_t)bi + 1]) continue;
+        const bydb_block_desc &bd = hb[(size_t)bi];
+        const uint8_t tenc = bd.ts_enc_with_version;
+        const uint8_t tc = tenc >= BYDB_ENC_CONST_WV ? tenc - 4 : tenc;
+        if (tc < BYDB_ENC_CONST || tc > BYDB_ENC_DELTA_OF_DELTA ||
+            bd.version_enc < BYDB_ENC_CONST ||
+            bd.version_enc > BYDB_ENC_DELTA_OF_DELTA || bd.count < 1 ||
+            bd.count > PLAIN_BM_WORDS * 64) {
+            char buf[128];
+            snprintf(buf, sizeof buf,
+                     "row dedup: block %lld has an unsupported timestamp / "
+                     "version encoding or row count", (long long)bi);
+            s->err = buf;
+            return BYDB_ERR_BAD_DATA;
+        }
+        DedupInfo in;
+        memset(&in, 0, sizeof in);
+        in.block = (uint32_t)bi;
+        in.count = bd.count;
+        in.ts_min = bd.ts_min;
+        in.ts_max = bd.ts_max;
+        in.ver_first = bd.version_first;
+        in.ts_kind = tc == BYDB_ENC_CONST ? DD_TS_CONST
+                     : tc == BYDB_ENC_DELTA_CONST ? DD_TS_ARITH : DD_TS_ARENA;
+        in.ts_arena = DD_NO_ARENA;
+        in.ver_arena = DD_NO_ARENA;
+        if (in.ts_kind == DD_TS_ARENA) {
+            in.ts_arena = arena_rows;
+            arena_rows += bd.count;
+        }
+        if (bd.version_enc != BYDB_ENC_CONST) {
+            in.ver_arena = arena_rows;
+            arena_rows += bd.count;
+        }
+        inv_of[(size_t)bi] = (uint32_t)infos.size();
+        infos.push_back(in);
+        ioffs.push_back(offs[(size_t)bi + 1]);
+    }
+    // ioffs holds each involved block's END in the block-indexed list; the
+    // lists of uninvolved blocks are empty, so these are also the offsets
+    // of the compacted list
+    for (size_t k = 0; k < pl.size(); k++) pl[k] = inv_of[pl[k]];
+    const int64_t n_inv = (int64_t)infos.size();
+    int rc;
+    if ((rc = dedup_alloc(s, &s->d_dd_infos, (uint64_t)n_inv, "block table")) ||
+        (rc = dedup_alloc(s, &s->d_dd_peer_offs, (uint64_t)n_inv + 1,
+                          "peer offsets")) ||
+        (rc = dedup_alloc(s, &s->d_dd_peers, pl.size(), "peer list")) ||
+        (rc = dedup_alloc(s, &s->d_dd_arena, arena_rows,
+                          "timestamp / version arena")) ||
+        (rc = dedup_alloc(s, &s->d_dd_surv,
+                          (uint64_t)n_inv * PLAIN_BM_WORDS,
+                          "survivor bitmaps")) ||
+        (rc = dedup_alloc(s, &s->d_dd_plist, (uint64_t)n_inv, "block lists")) ||
+        (rc = dedup_alloc(s, &s->d_dd_flist, (uint64_t)n_inv, "block lists")) ||
+        (rc = dedup_alloc(s, &s->d_dd_ctr, 4, "counters")))
+        return rc;
+    HIP_TRY(s, hipMemcpyAsync(s->d_dd_infos, infos.data(),
+                              sizeof(DedupInfo) * infos.size(),
+                              hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(s->d_dd_peer_offs, ioffs.data(),
+                              sizeof(uint64_t) * ioffs.size(),
+                              hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(s->d_dd_peers, pl.data(),
+                              sizeof(uint32_t) * pl.size(),
+                              hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(s, hipMemsetAsync(s->d_dd_ctr, 0, 4 * sizeof(unsigned long long),
+                              s->stream));
+    const int grid = (int)(n_inv < 65535 ? n_inv : 65535);
+    hipLaunchKernelGGL(k_dedup_decode, dim3(grid), dim3(WAVE), 0, s->stream,
+                       s->d_payload, s->payload_cap + 4096, s->d_blocks,
+                       s->d_dd_infos, n_inv, s->d_dd_arena, s->d_err);
+    HIP_TRY(s, hipGetLastError());
+    hipLaunchKernelGGL(k_dedup_mark, dim3(grid), dim3(WAVE), 0, s->stream,
+                       s->d_dd_infos, n_inv, s->d_dd_peer_offs, s->d_dd_peers,
+                       s->d_dd_arena, s->d_dd_surv, s->d_dd_plist,
+                       s->d_dd_flist, s->d_dd_ctr);
+    HIP_TRY(s, hipGetLastError());
+    unsigned long long h_ctr[4] = {0, 0, 0, 0};
+    DevErr de;
+    HIP_TRY(s, hipMemcpyAsync(h_ctr, s->d_dd_ctr, sizeof h_ctr,
+                              hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(&de, s->d_err, sizeof de, hipMemcpyDeviceToHost,
+                              s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    s->dd_n_inv = n_inv;
+    s->dd_n_partial = (int64_t)h_ctr[DD_CTR_PARTIAL];
+    s->dd_n_full = (int64_t)h_ctr[DD_CTR_FULL];
+    s->dedup_stats[0] = (uint64_t)n_inv;
+    s->dedup_stats[1] = h_ctr[DD_CTR_PARTIAL];
+    s->dedup_stats[2] = h_ctr[DD_CTR_FULL];
+    s->dedup_stats[3] = h_ctr[DD_CTR_ROWS];
+    // a device error (descending or unparseable stream) stays in d_err for
+    // finalize to report; the build is then repeated by the next consume,
+    // so a reset does not turn it into a silently unmerged scan
+    s->dedup_built = de.code == DERR_NONE;
+    return BYDB_OK;
+}
+
+// the part holds superseded rows and the session wants them dropped
+static bool dedup_active(const bydb_session *s) {
+    return s->row_dedup && s->dedup_built && s->dedup_stats[3] > 0;
+}
+
+// pred_bm words the merged bitmaps of this consume add to the demand
+static uint64_t dedup_bm_words(const bydb_session *s) {
+    return dedup_active(s) ? (uint64_t)s->dd_n_partial * PLAIN_BM_WORDS : 0;
+}
+
+// Grow the one pred_bm arena the scan receives to `words` (contents are
+// not kept: every consume fills it again before the scan reads it).
+static int ensure_pred_bm(bydb_session *s, uint64_t words) {
+    if (words <= s->pred_bm_cap) return BYDB_OK;
+    if (s->d_pred_bm) { (void)hipFree(s->d_pred_bm); s->d_pred_bm = nullptr; }
+    s->pred_bm_cap = 0;
+    HIP_TRY(s, hipMalloc(&s->d_pred_bm, words * sizeof(uint64_t)));
+    s->pred_bm_cap = words;
+    return BYDB_OK;
+}
+
+// The single point where every consume entry point reaches launch_scan.
+// n_slots is what the resolve stage resolved (0: unfiltered).  Without
+// superseded rows this is launch_scan itself — the same instantiations,
+// the same arguments, no extra launch.  With them, k_dedup_apply rewrites
+// the resolve output first (an unfiltered consume gets an all-CLEAR flag
+// table to rewrite) and the scan runs with at least one predicate slot.
+static int scan_deduped(bydb_session *s, int64_t min_ts, int64_t max_ts,
+                        PredBlock *preds, int n_slots) {
+    if (!dedup_active(s)) return launch_scan(s, min_ts, max_ts, preds, n_slots);
+    if (n_slots == 0) {
+        int rc = ensure_pred_buffers(s);
+        if (rc != BYDB_OK) return rc;
+        HIP_TRY(s, hipMemsetAsync(s->d_pred_flags, PF_CLEAR,
+                                  (size_t)s->n_blocks, s->stream));
+        rc = ensure_pred_bm(s, dedup_bm_words(s));
+        if (rc != BYDB_OK) return rc;
+        s->dd_bm_base = 0;
+    }
+    int64_t route_wgs = (s->dd_n_full + WAVE - 1) / WAVE;
+    int64_t want = s->dd_n_partial > route_wgs ? s->dd_n_partial : route_wgs;
+    int grid = (int)(want < 1 ? 1 : want < 65535 ? want : 65535);
+    hipLaunchKernelGGL(k_dedup_apply, dim3(grid), dim3(WAVE), 0, s->stream,
+                       s->d_payload, s->d_sidecar, s->d_blocks, s->n_blocks,
+                       s->d_dd_plist, s->dd_n_partial, s->d_dd_flist,
+                       s->dd_n_full, s->d_dd_surv, s->d_preds, n_slots,
+                       s->d_pred_flags, s->d_pred_bm, s->dd_bm_base,
+                       s->d_walk_count);
+    HIP_TRY(s, hipGetLastError());
+    return launch_scan(s, min_ts, max_ts, s->d_preds,
+                       n_slots > 1 ? n_slots : 1);
+}
+
 extern "C" int bydb_consume(bydb_session *s, int64_t min_ts, int64_t max_ts,
                             const uint8_t *pred, uint64_t pred_len) {
     if (pred_len == 0) {
@@ -4617,10 +5365,12 @@ static int build_filter_set(bydb_session *s, const bydb_tag_cond *conds,
 // conditions already validated: the two resolves feed the scan launch.
 static int consume_conds(bydb_session *s, int64_t min_ts, int64_t max_ts,
                          const bydb_tag_cond *conds, int n_conds) {
-    if (n_conds == 0) return launch_scan(s, min_ts, max_ts, nullptr, 0);
+    int rc = dedup_build(s);
+    if (rc != BYDB_OK) return rc;
+    if (n_conds == 0) return scan_deduped(s, min_ts, max_ts, nullptr, 0);
     FilterSet fs;
     int order[BYDB_FILTER_MAX_CONDS];
-    int rc = build_filter_set(s, conds, n_conds, &fs, order);
+    rc = build_filter_set(s, conds, n_conds, &fs, order);
     if (rc != BYDB_OK) return rc;
     rc = ensure_pred_buffers(s);
     if (rc != BYDB_OK) return rc;
@@ -4632,14 +5382,12 @@ static int consume_conds(bydb_session *s, int64_t min_ts, int64_t max_ts,
                        s->d_walk_count);
     HIP_TRY(s, hipGetLastError());
     // plain columns: one bitmap per normalized (block,slot) stream at most,
-    // counted at part_append — the arena is sized without a round-trip
+    // counted at part_append — the arena is sized without a round-trip;
+    // the dedup-merged bitmaps (count known from the build) follow them
+    s->dd_bm_base = s->n_plain_host * PLAIN_BM_WORDS;
+    rc = ensure_pred_bm(s, s->dd_bm_base + dedup_bm_words(s));
+    if (rc != BYDB_OK) return rc;
     if (s->n_plain_host > 0) {
-        uint64_t words = s->n_plain_host * PLAIN_BM_WORDS;
-        if (words > s->pred_bm_cap) {
-            if (s->d_pred_bm) (void)hipFree(s->d_pred_bm);
-            HIP_TRY(s, hipMalloc(&s->d_pred_bm, words * sizeof(uint64_t)));
-            s->pred_bm_cap = words;
-        }
         HIP_TRY(s, hipMemsetAsync(s->d_plain_ctr, 0, sizeof(uint32_t),
                                   s->stream));
         int pgrid = (int)(s->n_blocks < 65535 ? s->n_blocks : 65535);
@@ -4653,7 +5401,7 @@ static int consume_conds(bydb_session *s, int64_t min_ts, int64_t max_ts,
             HIP_TRY(s, hipGetLastError());
         }
     }
-    return launch_scan(s, min_ts, max_ts, s->d_preds, fs.n_slots);
+    return scan_deduped(s, min_ts, max_ts, s->d_preds, fs.n_slots);
 }
 
 // ---- criteria trees (header: "AND / OR criteria trees") ----
@@ -4775,6 +5523,8 @@ extern "C" int bydb_consume_filter_tree(bydb_session *s, int64_t min_ts,
     rc = tree_table(nodes, n_nodes, n_conds, ts.tt, &has_or, &why);
     if (rc != BYDB_OK) { s->err = why; return rc; }
     if (!has_or) return consume_conds(s, min_ts, max_ts, conds, n_conds);
+    rc = dedup_build(s);
+    if (rc != BYDB_OK) return rc;
 
     FilterSet fs;
     int order[BYDB_FILTER_MAX_CONDS];
@@ -4800,16 +5550,13 @@ extern "C" int bydb_consume_filter_tree(bydb_session *s, int64_t min_ts,
     HIP_TRY(s, hipStreamSynchronize(s->stream));
     for (int i = 0; i < 4; i++) s->tree_stats[i] = h_stats[i];
     const uint64_t n_row_blocks = h_stats[3];
+    // one bitmap per row-bitmap block, then the dedup-merged bitmaps; the
+    // arena only grows and is shared with the plain-column bitmaps of
+    // consume_conds
+    s->dd_bm_base = n_row_blocks * PLAIN_BM_WORDS;
+    rc = ensure_pred_bm(s, s->dd_bm_base + dedup_bm_words(s));
+    if (rc != BYDB_OK) return rc;
     if (n_row_blocks > 0) {
-        // one bitmap per row-bitmap block; the arena only grows and is
-        // shared with the plain-column bitmaps of consume_conds
-        uint64_t words = n_row_blocks * PLAIN_BM_WORDS;
-        if (words > s->pred_bm_cap) {
-            if (s->d_pred_bm) { (void)hipFree(s->d_pred_bm); s->d_pred_bm = nullptr; }
-            s->pred_bm_cap = 0;
-            HIP_TRY(s, hipMalloc(&s->d_pred_bm, words * sizeof(uint64_t)));
-            s->pred_bm_cap = words;
-        }
         HIP_TRY(s, hipMemsetAsync(s->d_plain_ctr, 0, sizeof(uint32_t),
                                   s->stream));
         int pgrid = (int)(s->n_blocks < 65535 ? s->n_blocks : 65535);
@@ -4820,7 +5567,7 @@ extern "C" int bydb_consume_filter_tree(bydb_session *s, int64_t min_ts,
                            s->pred_bm_cap / PLAIN_BM_WORDS);
         HIP_TRY(s, hipGetLastError());
     }
-    return launch_scan(s, min_ts, max_ts, s->d_preds, fs.n_slots);
+    return scan_deduped(s, min_ts, max_ts, s->d_preds, fs.n_slots);
 }
 
 // Equality predicates: one BYDB_OP_EQ string condition per non-empty slot.

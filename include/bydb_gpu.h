@@ -319,6 +319,71 @@ int bydb_filter_tree_table(const bydb_filter_node *nodes, int n_nodes,
  * unfiltered scan. */
 int bydb_filter_tree_stats(bydb_session *s, uint64_t out[4]);
 
+/* ---- cross-part version dedup (the measure query's merge) ----
+ * bydb_part_append accepts blocks from any number of on-disk parts.  When
+ * the same (seriesID, timestamp) appears in more than one of them — a
+ * re-sent data point, or a late correction flushed into a newer part that
+ * is not merged yet — the reference's measure query keeps exactly one row,
+ * the one with the highest version: for equal series and timestamp
+ * queryResult.Less orders versions descending, queryResult.merge copies the
+ * first row and lets a later row of the same timestamp replace it only when
+ * its version is greater than lastVersion (banyand/measure/
+ * query.go:913-943, 966-1026; TestQueryResult "multiple parts with
+ * duplicated data ...", query_test.go:61-1234).
+ *
+ * With row dedup on, a row (series_id, ts, version) of block b (b = block
+ * index in append order) is SUPERSEDED when another resident row has the
+ * same series_id and ts and either a greater version, or an equal version
+ * and a smaller block index.  Exactly one row per (series_id, ts) survives.
+ * The equal-version tie is unspecified in the reference (the heap order of
+ * equal keys is arbitrary); "the earliest appended block wins" is this
+ * engine's choice.
+ *
+ * Superseded rows do not exist for the rest of the query.  They are removed
+ * BEFORE tag conditions are evaluated, as the reference's merge sits below
+ * its filter: a higher-versioned row that fails the filter still hides the
+ * lower-versioned row that would have passed.  They contribute no group
+ * key, and a block whose rows are all superseded is a skipped block.
+ * Duplicates inside one block are the part builder's job (part.go:178,
+ * 192-198); blocks of different series never interact.
+ *
+ * Which rows survive is derived state over the resident part: it is built
+ * on the first consume with dedup on (that consume waits once for the
+ * build) and rebuilt after bydb_part_reserve / bydb_part_append.  A part
+ * without overlapping blocks, or without superseded rows, scans exactly as
+ * with dedup off.  A partially superseded block is scanned through a
+ * per-row bitmap predicate, so the bydb_group_first_seen caveat for bitmap
+ * predicates inside row-varying group merges applies to it. */
+
+/* Sticky per session, default 0 (off: nothing in the session changes).
+ * BYDB_ERR_BAD_ARG (session stays usable) for any value but 0 or 1.  If
+ * the build cannot allocate its device arenas, the consume returns
+ * BYDB_ERR_OOM naming the size and dedup is turned off. */
+int bydb_set_row_dedup(bydb_session *s, int on);
+
+/* What the build found (query.go:913-943, 966-1026 applied to the resident
+ * part): out[0] blocks that overlap at least one other block of their
+ * series, out[1] blocks with some but not all rows superseded, out[2]
+ * blocks with every row superseded, out[3] rows superseded.  Valid after
+ * the first consume with dedup on; all zero before that and whenever dedup
+ * is off. */
+int bydb_row_dedup_stats(bydb_session *s, uint64_t out[4]);
+
+/* Pure host, no GPU, no session: the overlap planner the device stage is
+ * driven by (the blocks whose cursors the reference's heap could ever
+ * compare, query.go:913-943).  Two blocks are peers when they have the
+ * same series_id and their [ts_min, ts_max] ranges intersect, both ends
+ * inclusive.  Output is a symmetric CSR: block i's peers are
+ * peers[peer_offs[i] .. peer_offs[i + 1]), ascending by block index.
+ * peer_offs (n_blocks + 1 entries) and *n_peers are always written;
+ * BYDB_ERR_OOM when peers_cap < *n_peers (peers is then untouched, so a
+ * first call with peers_cap 0 sizes the list), BYDB_ERR_BAD_ARG on null
+ * outputs. */
+int bydb_row_dedup_peers(const bydb_block_desc *blocks, int64_t n_blocks,
+                         uint64_t *peer_offs /* n_blocks + 1 */,
+                         uint32_t *peers, uint64_t peers_cap,
+                         uint64_t *n_peers);
+
 /* ---- finalize + emit (Finalize/NextBatch) ----
  * Syncs the stream, downloads partials and finalises per-group results
  * (MEAN = sum/count with the >=1 clamp; float64 restore per float.go).
