@@ -573,7 +573,9 @@ __device__ uint64_t dense_delta_weighted(const uint8_t *stream,
 // back to one 64-byte ballot step (exact same semantics), then resume.
 // The next window's dwords are loaded before the current one is processed
 // (the fast path's advance is a compile-time +256), hiding HBM latency.
-__device__ uint64_t fold_delta_weighted_fast(const uint8_t *stream,
+// Inlined into its one caller, fold_rows, like fold_dod_weighted below: as
+// calls they cost the clamped value-scan light pass 64 bytes of scratch.
+__device__ __forceinline__ uint64_t fold_delta_weighted_fast(const uint8_t *stream,
                                              int64_t n_deltas, int64_t r0,
                                              int64_t r1, int lane, DevErr *derr,
                                              uint64_t bi) {
@@ -700,7 +702,7 @@ __device__ uint64_t fold_delta_weighted_fast(const uint8_t *stream,
 // Weighted delta-of-delta fold: sum_{i=r0..r1} v_i with
 //   v_i = first + i*d1 + sum_{k=2..i} d2_k * (i-k+1)
 // => contribution of d2_k (k in [2, r1]):  W_k = T(r1-k+1) - T(max(k,r0)-k).
-__device__ uint64_t fold_dod_weighted(const uint8_t *stream, int64_t n_deltas,
+__device__ __forceinline__ uint64_t fold_dod_weighted(const uint8_t *stream, int64_t n_deltas,
                                       int64_t r0, int64_t r1, int lane,
                                       DevErr *derr, uint64_t bi) {
     uint64_t acc = 0;
@@ -866,6 +868,19 @@ __device__ __forceinline__ bool pred_match_rows(PredWalk *pw, int64_t row,
         pred_advance(pw);
     }
     return match;
+}
+
+// The conjunction of up to three walkers for each lane's row.  Every lane
+// calls every walker (RLE walkers advance wave-wide); a lane that already
+// failed a slot stops needing the later ones.
+__device__ __forceinline__ bool walkers_match(PredWalk *w0, PredWalk *w1,
+                                              PredWalk *w2, int64_t row,
+                                              bool need) {
+    bool ok = true;
+    if (w0) ok = pred_match_rows(w0, row, need && ok) && ok;
+    if (w1) ok = pred_match_rows(w1, row, need && ok) && ok;
+    if (w2) ok = pred_match_rows(w2, row, need && ok) && ok;
+    return ok;
 }
 
 // ---- per-row group-by on a dictionary tag ----
@@ -1930,10 +1945,7 @@ __device__ void fold_arith_pred(int64_t first, int64_t dd, int64_t r0,
     for (int64_t base = r0; base <= r1; base += 64) {
         int64_t row = base + lane;
         bool need = row <= r1;
-        bool match = true;
-        if (pw0) match = pred_match_rows(pw0, row, need && match) && match;
-        if (pw1) match = pred_match_rows(pw1, row, need && match) && match;
-        if (pw2) match = pred_match_rows(pw2, row, need && match) && match;
+        bool match = walkers_match(pw0, pw1, pw2, row, need);
         if (need && match) {
             int64_t v = (int64_t)((uint64_t)first + (uint64_t)row * (uint64_t)dd);
             lsum += (uint64_t)v;
@@ -2611,64 +2623,57 @@ enum {
                          // the light/heavy predicate split below)
 };
 
-// wfirst: the (item << 13 | row) key where this wave first ENTERED the
-// group (rows that pass predicates and map to the group, before the
-// null-field check — matching where the reference's computeKey
-// materialises a group, aggregation.go:523).  The global atomicMin over
-// these keys is the group's first appearance in storage order, which is
-// the reference's first-seen materialisation order (blocks iterate in
-// (sid, minTs) order, rows ascend).  ~0 = no entry this flush.
-__device__ __forceinline__ void flush_partial(bydb_partial *partials,
-                                              int64_t group, uint64_t wsum,
-                                              uint64_t wcnt, int64_t wmin,
-                                              int64_t wmax, double wsumf,
-                                              int lane,
-                                              uint64_t *first_seen,
-                                              uint64_t wfirst) {
-    if (group < 0 || lane != 0) return;
-    bydb_partial *p = &partials[group];
-    if (first_seen != nullptr && wfirst != ~0ull)
-        atomicMin((unsigned long long *)&first_seen[group],
-                  (unsigned long long)wfirst);
-    if (wsum) atomicAdd((unsigned long long *)&p->sum_i, (unsigned long long)wsum);
-    if (wcnt) atomicAdd((unsigned long long *)&p->count, (unsigned long long)wcnt);
-    if (wmin != INT64_MAX) atomicMin((long long *)&p->min_i, (long long)wmin);
-    if (wmax != INT64_MIN) atomicMax((long long *)&p->max_i, (long long)wmax);
-    if (wsumf != 0.0) atomicAdd(&p->sum_f, wsumf);
-}
+// What folding rows [a, b] of one block's field column gives.  sum is the
+// wrapping sum (in a raw-float session: the bits of the double sum) and is
+// wave-uniform, as are the rest.
+struct RowFold {
+    uint64_t sum;
+    uint64_t cnt;       // rows folded: selected, matching and not null
+    int64_t mn, mx;
+    bool have_mm;       // mn/mx hold values
+};
 
-// Fold rows [a, b] of a block's field column: returns the wrapping sum,
-// selected count and optional min/max.  Shared by the per-run grouped
-// fold; mirrors the main kernel's dispatch.  bw0..bw2: optional
-// BITMAP-mode predicate walkers (plain >256-card tag columns,
-// k_resolve_plain) — stateless O(1) per-row lookups, so they filter any
-// sub-range; RLE walkers never reach here (the run merge intersects
-// their runs into [a, b] instead).
-__device__ void fold_range(const uint8_t *fstream, uint8_t fenc, int64_t first,
-                           uint64_t field_len, int64_t n, int64_t a, int64_t b,
-                           bool need_values, int lane, uint64_t *out_sum,
-                           int64_t *out_mn, int64_t *out_mx, bool *out_have_mm,
-                           uint64_t *out_cnt, const uint8_t *plain_norm,
-                           bool raw_f64, DevErr *derr, uint64_t bi,
-                           PredWalk *bw0 = nullptr, PredWalk *bw1 = nullptr,
-                           PredWalk *bw2 = nullptr) {
-    uint64_t nsel = (uint64_t)(b - a + 1);
-    uint64_t bsum = 0;
-    int64_t bmn = INT64_MAX, bmx = INT64_MIN;
-    bool have = false;
-    *out_cnt = nsel;
+// How fold_rows reaches the dense one-byte Delta closed form.
+enum {
+    DENSE_CALL,         // the out-of-line dense_delta_weighted
+    DENSE_INLINE,       // dense_delta_weighted_t inlined, whole block in flight
+    DENSE_INLINE_NT,    // the same with non-temporal loads
+};
+
+// Fold rows [a, b] of a block's field column — the one field fold, for the
+// scan kernel's [r0, r1] and for the sub-ranges of the grouped run merge.
+// w0..w2: optional row-varying predicate walkers; rows must ascend, which
+// they do within one call.  plain_norm: the host-normalized cells of a
+// Plain block (nullptr when the block was not normalized).
+// Compile-time: EN_VALUES — min/max reconstruction can be asked for at all;
+// FULL — [a, b] is promised to cover every streamed row (scan_stream drops
+// its selection branch); DENSE — see the enum above.
+template <bool EN_VALUES, bool FULL, int DENSE>
+__device__ __forceinline__ RowFold fold_rows(
+    const uint8_t *fstream, const uint8_t *plain_norm, uint8_t fenc,
+    int64_t first, uint64_t field_len, int64_t n, int64_t a, int64_t b,
+    bool need_values, bool raw_f64, int lane, PredWalk *w0, PredWalk *w1,
+    PredWalk *w2, DevErr *derr, uint64_t bi) {
+    need_values = EN_VALUES && need_values;
+    const uint64_t nsel = (uint64_t)(b - a + 1);
+    const bool pred_on = w0 || w1 || w2;
+    RowFold f = {0, nsel, INT64_MAX, INT64_MIN, false};
     if (fenc == BYDB_ENC_PLAIN) {
-        // null-bearing cell block (host-normalized; see the main Plain
-        // fold branch): count excludes nulls
-        if (!plain_norm) {
+        // null-bearing Plain column, host-normalized into the sidecar
+        // ([u32 n][pad][validity bitmap][8-B sign-flip cells]): fold
+        // valid selected rows, decoding cells in-lane
+        // (convert/number.go:95-108); nulls drop from count and every
+        // aggregate (aggregation.go:310).
+        uint32_t nn = 0;
+        if (plain_norm)
+            nn = (uint32_t)plain_norm[0] | ((uint32_t)plain_norm[1] << 8) |
+                 ((uint32_t)plain_norm[2] << 16) |
+                 ((uint32_t)plain_norm[3] << 24);
+        if (!plain_norm || nn != (uint32_t)n) {
             dev_set_err(derr, DERR_BAD_ENC, bi);
-            *out_sum = 0; *out_mn = bmn; *out_mx = bmx; *out_have_mm = false;
-            *out_cnt = 0;
-            return;
+            f.cnt = 0;
+            return f;
         }
-        uint32_t nn = (uint32_t)plain_norm[0] | ((uint32_t)plain_norm[1] << 8) |
-                      ((uint32_t)plain_norm[2] << 16) |
-                      ((uint32_t)plain_norm[3] << 24);
         const uint64_t *vbm = (const uint64_t *)(plain_norm + 8);
         const uint64_t *cells = vbm + ((uint64_t)nn + 63) / 64;
         uint64_t lsum = 0, lcnt = 0;
@@ -2677,221 +2682,289 @@ __device__ void fold_range(const uint8_t *fstream, uint8_t fenc, int64_t first,
         for (int64_t base = a; base <= b; base += WAVE) {
             int64_t row = base + lane;
             bool ok = row <= b && ((vbm[row >> 6] >> (row & 63)) & 1);
-            if (bw0) ok = pred_match_rows(bw0, row, ok) && ok;
-            if (bw1) ok = pred_match_rows(bw1, row, ok) && ok;
-            if (bw2) ok = pred_match_rows(bw2, row, ok) && ok;
+            ok = walkers_match(w0, w1, w2, row, ok) && ok;
             if (ok) {
+                // cells are big-endian on the wire
                 uint64_t u = __builtin_bswap64(cells[row]);
+                int64_t v;
                 if (raw_f64) {
+                    // IEEE-754 bits: double sum + ordered-bits min/max
+                    // (Float64ToOrderedBytes map,
+                    // convert/number.go:148-157)
                     double dv;
                     __builtin_memcpy(&dv, &u, 8);
                     lsumf += dv;
-                    int64_t kv = (u >> 63)
-                                     ? (int64_t)(~u ^ 0x8000000000000000ull)
-                                     : (int64_t)u;
-                    lmn = kv < lmn ? kv : lmn;
-                    lmx = kv > lmx ? kv : lmx;
+                    // order-preserving map INTO THE SIGNED domain
+                    // (min/max compare as int64): positives keep raw
+                    // bits, negatives flip magnitude and sign
+                    v = (u >> 63) ? (int64_t)(~u ^ 0x8000000000000000ull)
+                                  : (int64_t)u;
                 } else {
-                    int64_t v = (u >> 63) ? (int64_t)(u & ~(1ull << 63))
-                                          : -(int64_t)((1ull << 63) - u);
+                    v = (u >> 63) ? (int64_t)(u & ~(1ull << 63))
+                                  : -(int64_t)((1ull << 63) - u);
                     lsum += (uint64_t)v;
-                    lmn = v < lmn ? v : lmn;
-                    lmx = v > lmx ? v : lmx;
                 }
+                lmn = v < lmn ? v : lmn;
+                lmx = v > lmx ? v : lmx;
                 lcnt++;
             }
         }
         if (raw_f64) {
             double ds = wave_reduce_addf(lsumf);
-            uint64_t db;
-            __builtin_memcpy(&db, &ds, 8);
-            bsum = db;
+            __builtin_memcpy(&f.sum, &ds, 8);
         } else {
-            bsum = wave_reduce_add(lsum);
+            f.sum = wave_reduce_add(lsum);
         }
-        *out_cnt = wave_reduce_add(lcnt);
-        bmn = wave_reduce_min(lmn);
-        bmx = wave_reduce_max(lmx);
-        have = *out_cnt > 0;
-        *out_sum = bsum;
-        *out_mn = bmn;
-        *out_mx = bmx;
-        *out_have_mm = have;
-        return;
+        f.cnt = wave_reduce_add(lcnt);
+        f.mn = wave_reduce_min(lmn);
+        f.mx = wave_reduce_max(lmx);
+        f.have_mm = f.cnt > 0;
+        return f;
     }
-    if (bw0 || bw1 || bw2) {
-        // bitmap-filtered fold over the non-Plain encodings: arithmetic
-        // progressions via the predicated row walk, varint streams via
-        // the walker-aware scan (the closed forms cannot filter rows)
-        if (fenc == BYDB_ENC_CONST || fenc == BYDB_ENC_DELTA_CONST) {
-            int64_t dd = 0;
-            if (fenc == BYDB_ENC_DELTA_CONST) {
-                int vl;
-                dd = decode_one_varint(fstream, &vl);
-            }
+    if (fenc == BYDB_ENC_CONST || fenc == BYDB_ENC_DELTA_CONST) {
+        int64_t dd = 0;
+        if (fenc == BYDB_ENC_DELTA_CONST) {
+            int vl;
+            dd = decode_one_varint(fstream, &vl);
+        }
+        if (pred_on) {
+            // the closed forms cannot filter rows: predicated row walk
             uint64_t psum, pcnt;
-            fold_arith_pred(first, dd, a, b, lane, bw0, bw1, bw2, &psum,
-                            &pcnt, &bmn, &bmx);
-            *out_sum = psum;   // wave_reduce_add already wave-uniform
-            *out_cnt = pcnt;
-            *out_mn = bmn;
-            *out_mx = bmx;
-            *out_have_mm = pcnt > 0;
-            return;
+            int64_t pmn, pmx;
+            fold_arith_pred(first, dd, a, b, lane, w0, w1, w2, &psum, &pcnt,
+                            &pmn, &pmx);
+            f.sum = psum;
+            f.cnt = pcnt;
+            f.mn = pmn;
+            f.mx = pmx;
+            f.have_mm = need_values && pcnt > 0;
+            return f;
         }
-        if (fenc == BYDB_ENC_DELTA || fenc == BYDB_ENC_DELTA_OF_DELTA) {
-            bool dod = fenc == BYDB_ENC_DELTA_OF_DELTA;
-            const uint8_t *st = fstream;
-            int64_t d1 = 0;
-            if (dod) {
-                int vl;
-                d1 = decode_one_varint(st, &vl);
-                st += vl;
-            }
-            int64_t row1 = (int64_t)((uint64_t)first + (uint64_t)d1);
-            uint64_t lsum = 0, lcnt = 0;
+        // sum_{i=a..b}(first + i*dd) = nsel*first + dd * sum i
+        uint64_t si = (uint64_t)(a + b) * nsel / 2;
+        f.sum = (uint64_t)first * nsel + (uint64_t)dd * si;
+        if (fenc == BYDB_ENC_CONST) {
+            f.mn = f.mx = first;
+            f.have_mm = true;
+        } else if (need_values) {
+            // reconstruct min/max exactly (wrap-safe): walk rows by lanes
             int64_t lmn = INT64_MAX, lmx = INT64_MIN;
-            bool need0 = lane == 0 && a <= 0 && 0 <= b;
-            bool m0 = true;
-            if (bw0) m0 = pred_match_rows(bw0, 0, need0 && m0) && m0;
-            if (bw1) m0 = pred_match_rows(bw1, 0, need0 && m0) && m0;
-            if (bw2) m0 = pred_match_rows(bw2, 0, need0 && m0) && m0;
-            if (need0 && m0) {
-                lsum += (uint64_t)first;
-                lcnt++;
-                lmn = first;
-                lmx = first;
-            }
-            if (dod) {
-                bool need1 = lane == 0 && a <= 1 && 1 <= b;
-                bool m1 = true;
-                if (bw0) m1 = pred_match_rows(bw0, 1, need1 && m1) && m1;
-                if (bw1) m1 = pred_match_rows(bw1, 1, need1 && m1) && m1;
-                if (bw2) m1 = pred_match_rows(bw2, 1, need1 && m1) && m1;
-                if (need1 && m1) {
-                    lsum += (uint64_t)row1;
-                    lcnt++;
-                    lmn = row1 < lmn ? row1 : lmn;
-                    lmx = row1 > lmx ? row1 : lmx;
-                }
-            }
-            ScanFold ff;
-            scan_stream(st, n - 1, dod, dod ? row1 : first, d1, a, b,
-                        lane, &ff, derr, bi, bw0, bw1, bw2);
-            lsum += ff.sum;
-            lcnt += ff.nsel;
-            lmn = ff.mn < lmn ? ff.mn : lmn;
-            lmx = ff.mx > lmx ? ff.mx : lmx;
-            uint64_t wsum2 = wave_reduce_add(lsum);
-            *out_cnt = wave_reduce_add(lcnt);
-            *out_mn = wave_reduce_min(lmn);
-            *out_mx = wave_reduce_max(lmx);
-            *out_have_mm = *out_cnt > 0;
-            *out_sum = wsum2;
-            return;
-        }
-        dev_set_err(derr, DERR_BAD_ENC, bi);
-        *out_sum = 0;
-        *out_mn = bmn;
-        *out_mx = bmx;
-        *out_have_mm = false;
-        *out_cnt = 0;
-        return;
-    }
-    if (fenc == BYDB_ENC_CONST) {
-        if (lane == 0) bsum = (uint64_t)first * nsel;
-        bmn = bmx = first;
-        have = true;
-    } else if (fenc == BYDB_ENC_DELTA_CONST) {
-        int vl;
-        int64_t dd = decode_one_varint(fstream, &vl);
-        if (lane == 0) {
-            uint64_t si = (uint64_t)(a + b) * nsel / 2;
-            bsum = (uint64_t)first * nsel + (uint64_t)dd * si;
-        }
-        if (need_values) {
-            int64_t lmn = INT64_MAX, lmx = INT64_MIN;
-            for (int64_t base = a; base <= b; base += 64) {
+            for (int64_t base = a; base <= b; base += WAVE) {
                 int64_t i = base + lane;
                 if (i <= b) {
-                    int64_t v = (int64_t)((uint64_t)first + (uint64_t)i * (uint64_t)dd);
+                    int64_t v = (int64_t)((uint64_t)first +
+                                          (uint64_t)i * (uint64_t)dd);
                     lmn = v < lmn ? v : lmn;
                     lmx = v > lmx ? v : lmx;
                 }
             }
-            bmn = wave_reduce_min(lmn);
-            bmx = wave_reduce_max(lmx);
-            have = true;
+            f.mn = wave_reduce_min(lmn);
+            f.mx = wave_reduce_max(lmx);
+            f.have_mm = true;
         }
-    } else if (fenc == BYDB_ENC_DELTA) {
-        uint64_t acc;
-        bool dense = field_len == (uint64_t)(n - 1);
-        if (dense) acc = dense_delta_weighted(fstream, n - 1, a, b, lane);
-        else acc = fold_delta_weighted_fast(fstream, n - 1, a, b, lane, derr, bi);
-        acc = wave_reduce_add(acc);
-        if (lane == 0) bsum = (uint64_t)first * nsel + acc;
-        if (need_values) {
-            if (dense) {
-                int64_t psd, psjd;
-                dense_region(fstream, 0, a, lane, &psd, &psjd);
-                int64_t vr0 = (int64_t)((uint64_t)first +
-                                        wave_reduce_add((uint64_t)psd));
-                dense_minmax(fstream, a, b, vr0, lane, &bmn, &bmx);
-                bmn = vr0 < bmn ? vr0 : bmn;
-                bmx = vr0 > bmx ? vr0 : bmx;
-            } else {
-                ScanFold ff;
-                scan_stream(fstream, n - 1, false, first, 0, a, b,
-                            lane, &ff, derr, bi, nullptr, nullptr,
-                            nullptr);
-                int64_t lmn = ff.mn, lmx = ff.mx;
-                if (lane == 0 && a <= 0 && 0 <= b) {
-                    lmn = first < lmn ? first : lmn;
-                    lmx = first > lmx ? first : lmx;
-                }
-                bmn = wave_reduce_min(lmn);
-                bmx = wave_reduce_max(lmx);
-            }
-            have = true;
-        }
-    } else if (fenc == BYDB_ENC_DELTA_OF_DELTA) {
-        int vl;
-        int64_t d1 = decode_one_varint(fstream, &vl);
-        uint64_t acc = fold_dod_weighted(fstream + vl, n - 1, a, b, lane, derr, bi);
-        acc = wave_reduce_add(acc);
-        if (lane == 0) {
-            uint64_t si = (uint64_t)(a + b) * nsel / 2;
-            bsum = (uint64_t)first * nsel + (uint64_t)d1 * si + acc;
-        }
-        if (need_values) {
-            int64_t row1 = (int64_t)((uint64_t)first + (uint64_t)d1);
-            ScanFold ff;
-            scan_stream(fstream + vl, n - 1, true, row1, d1, a, b,
-                        lane, &ff, derr, bi, nullptr, nullptr,
-                        nullptr);
-            int64_t lmn = ff.mn, lmx = ff.mx;
-            if (lane == 0) {
-                if (a <= 0 && 0 <= b) {
-                    lmn = first < lmn ? first : lmn;
-                    lmx = first > lmx ? first : lmx;
-                }
-                if (a <= 1 && 1 <= b) {
-                    lmn = row1 < lmn ? row1 : lmn;
-                    lmx = row1 > lmx ? row1 : lmx;
-                }
-            }
-            bmn = wave_reduce_min(lmn);
-            bmx = wave_reduce_max(lmx);
-            have = true;
-        }
-    } else {
-        dev_set_err(derr, DERR_BAD_ENC, bi);
+        return f;
     }
-    *out_sum = (uint64_t)__shfl((long long)bsum, 0);
-    *out_mn = bmn;
-    *out_mx = bmx;
-    *out_have_mm = have;
+    if (fenc != BYDB_ENC_DELTA && fenc != BYDB_ENC_DELTA_OF_DELTA) {
+        dev_set_err(derr, DERR_BAD_ENC, bi);
+        f.cnt = 0;
+        return f;
+    }
+    const bool dod = fenc == BYDB_ENC_DELTA_OF_DELTA;
+    // stream length == delta count -> every varint is one byte
+    const bool dense = !dod && field_len == (uint64_t)(n - 1);
+    if (!pred_on && (!need_values || dense)) {
+        // closed forms: the weighted folds include first (and d1)
+        uint64_t acc;
+        int64_t d1 = 0;
+        if (dod) {
+            int vl;
+            d1 = decode_one_varint(fstream, &vl);
+            acc = fold_dod_weighted(fstream + vl, n - 1, a, b, lane, derr, bi);
+        } else if (!dense) {
+            acc = fold_delta_weighted_fast(fstream, n - 1, a, b, lane, derr,
+                                           bi);
+        } else if (DENSE == DENSE_CALL || need_values) {
+            acc = dense_delta_weighted(fstream, n - 1, a, b, lane);
+        } else {
+            // dense dot4 fold, the whole block in flight
+            acc = dense_delta_weighted_t<FULL ? DENSE_CHUNKS_BLOCK
+                                              : DENSE_CHUNKS_CLAMP,
+                                         DENSE == DENSE_INLINE_NT>(
+                fstream, n - 1, a, b, lane);
+        }
+        // nsel*first + d1 * sum_{i=a..b} i + the weighted deltas
+        uint64_t si = (uint64_t)(a + b) * nsel / 2;
+        f.sum = (uint64_t)first * nsel + (uint64_t)d1 * si +
+                wave_reduce_add(acc);
+        if (need_values) {
+            // dense min/max (no serial window chain):
+            // v at row a = first + sum of bytes [0, a)
+            int64_t psd, psjd;
+            dense_region(fstream, 0, a, lane, &psd, &psjd);
+            int64_t va = (int64_t)((uint64_t)first +
+                                   wave_reduce_add((uint64_t)psd));
+            dense_minmax(fstream, a, b, va, lane, &f.mn, &f.mx);
+            f.mn = va < f.mn ? va : f.mn;  // row a itself
+            f.mx = va > f.mx ? va : f.mx;
+            f.have_mm = true;
+        }
+        return f;
+    }
+    // value scan (predicated, or min/max over multi-byte varints)
+    const uint8_t *s = fstream;
+    int64_t d1 = 0;
+    if (dod) {
+        int vl;
+        d1 = decode_one_varint(s, &vl);
+        s += vl;
+    }
+    const int64_t row1 = (int64_t)((uint64_t)first + (uint64_t)d1);
+    uint64_t lsum = 0, lcnt = 0;
+    int64_t lmn = INT64_MAX, lmx = INT64_MIN;
+    // the rows the stream does not carry: row 0 (value first) and, for
+    // delta-of-delta, row 1 (value row1)
+    auto head_rows = [&]() {
+        for (int64_t row = 0; row <= (dod ? 1 : 0); row++) {
+            int64_t v = row ? row1 : first;
+            bool need = lane == 0 && a <= row && row <= b;
+            if (walkers_match(w0, w1, w2, row, need) && need) {
+                lsum += (uint64_t)v;
+                lcnt++;
+                lmn = v < lmn ? v : lmn;
+                lmx = v > lmx ? v : lmx;
+            }
+        }
+    };
+    // walker rows must ascend: under a predicate they come before the scan.
+    // Otherwise after it, so that nothing is live across its window loop.
+    if (pred_on) head_rows();
+    ScanFold ff;
+    scan_stream(s, n - 1, dod, dod ? row1 : first, d1, a, b, lane, &ff, derr,
+                bi, w0, w1, w2, FULL);
+    lsum += ff.sum;
+    lmn = ff.mn < lmn ? ff.mn : lmn;
+    lmx = ff.mx > lmx ? ff.mx : lmx;
+    if (!pred_on) head_rows();
+    f.sum = wave_reduce_add(lsum);
+    f.mn = wave_reduce_min(lmn);
+    f.mx = wave_reduce_max(lmx);
+    f.have_mm = true;
+    if (pred_on) {
+        f.cnt = wave_reduce_add(lcnt + ff.nsel);
+        f.have_mm = f.cnt > 0;
+    }
+    return f;
 }
+
+// The out-of-line instantiation, for the row-varying group-by run merge:
+// sub-ranges of a block, so never FULL.  Out of line because the grouped
+// kernels' register budget depends on it, and with the result behind a
+// pointer: returned by value it costs those kernels 150-290 bytes of
+// scratch each.  Only BITMAP-mode walkers
+// (plain >256-card tag columns, k_resolve_plain) reach here: their
+// stateless O(1) per-row lookups filter any sub-range, while the run merge
+// intersects the runs of RLE walkers into [a, b] instead.
+__device__ void fold_range(const uint8_t *fstream,
+                              const uint8_t *plain_norm, uint8_t fenc,
+                              int64_t first, uint64_t field_len, int64_t n,
+                              int64_t a, int64_t b, bool need_values,
+                              bool raw_f64, int lane, PredWalk *bw0,
+                              PredWalk *bw1, PredWalk *bw2, DevErr *derr,
+                              uint64_t bi, RowFold *out) {
+    *out = fold_rows<true, false, DENSE_CALL>(fstream, plain_norm, fenc, first,
+                                              field_len, n, a, b, need_values,
+                                              raw_f64, lane, bw0, bw1, bw2,
+                                              derr, bi);
+}
+
+// The per-wave partial: one group's running aggregates in registers.
+// One atomic set per BLOCK on a single group serialises on one cacheline
+// (~88 atomics/us on one word) and dominates the whole scan; instead block
+// totals fold into these registers and flush only when the group changes
+// or the wave is done.
+// first: the (item << 13 | row) key where this wave first ENTERED the
+// group (rows that pass predicates and map to the group, before the
+// null-field check — matching where the reference's computeKey
+// materialises a group, aggregation.go:523).  The global atomicMin over
+// these keys is the group's first appearance in storage order, which is
+// the reference's first-seen materialisation order (blocks iterate in
+// (sid, minTs) order, rows ascend).  ~0 = no entry this flush.
+struct WavePartial {
+    int64_t group = -1;
+    uint64_t sum = 0, cnt = 0;
+    uint64_t first = ~0ull;
+    int64_t mn = INT64_MAX, mx = INT64_MIN;
+    double sumf = 0.0;
+
+    __device__ __forceinline__ void flush(bydb_partial *partials,
+                                          uint64_t *first_seen,
+                                          int lane) const {
+        if (group < 0 || lane != 0) return;
+        bydb_partial *p = &partials[group];
+        if (first_seen != nullptr && first != ~0ull)
+            atomicMin((unsigned long long *)&first_seen[group],
+                      (unsigned long long)first);
+        if (sum) atomicAdd((unsigned long long *)&p->sum_i, (unsigned long long)sum);
+        if (cnt) atomicAdd((unsigned long long *)&p->count, (unsigned long long)cnt);
+        if (mn != INT64_MAX) atomicMin((long long *)&p->min_i, (long long)mn);
+        if (mx != INT64_MIN) atomicMax((long long *)&p->max_i, (long long)mx);
+        if (sumf != 0.0) atomicAdd(&p->sum_f, sumf);
+    }
+
+    // Merge one fold into group g, entered at `key`.  fdiff: the block's
+    // decimal exponent above the session's (float sessions): min/max
+    // mantissas rescale exactly by 10^fdiff, the sum by the same factor as
+    // a double.  A mantissa that overflows the rescale is a device error;
+    // the fold is then dropped whole (ovf_drops, returns false) or merged
+    // without its min/max.
+    __device__ __forceinline__ bool add(int64_t g, uint64_t key, RowFold f,
+                                        int flags, int fdiff, bool raw_f64,
+                                        bool ovf_drops, bydb_partial *partials,
+                                        uint64_t *first_seen, int lane,
+                                        DevErr *derr, uint64_t bi) {
+        double fscale = 1.0;
+        if ((flags & KF_FLOAT) && fdiff) {
+            int64_t mfac = c_pow10i[fdiff];
+            fscale = (double)mfac;
+            if (f.have_mm) {
+                int64_t smin, smax;
+                if (__builtin_mul_overflow(f.mn, mfac, &smin) ||
+                    __builtin_mul_overflow(f.mx, mfac, &smax)) {
+                    dev_set_err(derr, DERR_EXP_MISMATCH, bi);
+                    if (ovf_drops) return false;
+                    f.have_mm = false;
+                } else {
+                    f.mn = smin;
+                    f.mx = smax;
+                }
+            }
+        }
+        if (g != group) {
+            flush(partials, first_seen, lane);
+            *this = WavePartial();
+            group = g;
+            first = key;
+        } else if (first == ~0ull) {
+            first = key;
+        }
+        sum += f.sum;
+        cnt += f.cnt;
+        if (f.have_mm) {
+            mn = f.mn < mn ? f.mn : mn;
+            mx = f.mx > mx ? f.mx : mx;
+        }
+        if (flags & KF_FLOAT) {
+            if (raw_f64) {
+                double db;
+                __builtin_memcpy(&db, &f.sum, 8);
+                sumf += db;
+            } else {
+                sumf += (double)(int64_t)f.sum * fscale;
+            }
+        }
+        return true;
+    }
+};
 
 // Compile-time specialization: the FAST instantiation (no value
 // reconstruction, no predicates) sheds the scan/walker machinery and its
@@ -2979,12 +3052,7 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
     int64_t wave_id = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave_in_block;
     int64_t n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
 
-    // per-wave partial (flushed on group change / at the end)
-    int64_t cur_group = -1;
-    uint64_t wsum = 0, wcnt = 0;
-    uint64_t wfirst = ~0ull;   // first (item,row) entry key of cur_group
-    int64_t wmin = INT64_MAX, wmax = INT64_MIN;
-    double wsumf = 0.0;
+    WavePartial part;   // flushed on group change / at the end
 
     // with a segment index, the work item is a (block, segment) pair —
     // 8x the parallel units on the value-scan path, no serial chain.
@@ -3133,7 +3201,6 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
             }
             if (r0 > r1) continue;
         }
-        const uint64_t nsel = (uint64_t)(r1 - r0 + 1);
 
         // ---- per-row tag predicates (conjunctive, dictionary codes) ----
         // One combined flag byte decides the common cases; only PF_WALK
@@ -3203,7 +3270,7 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
                 // row-varying predicates join the run merge below:
                 // RLE walkers as additional run cursors; BITMAP-mode
                 // (plain-tag) walkers have no runs, so they filter
-                // per-row inside fold_range instead (stateless O(1)
+                // per-row inside the fold instead (stateless O(1)
                 // lookups — heavy-pass (EN_WALK) instantiations only)
                 PredWalk *bw0 = nullptr, *bw1 = nullptr, *bw2 = nullptr;
                 if (EN_WALK) {
@@ -3298,59 +3365,15 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
                     if (wp1) ok = ok && wp1->run_match;
                     if (wp2) ok = ok && wp2->run_match;
                     if (ok && aa <= bb2) {
-                        uint64_t rsum, rcnt;
-                        int64_t rmn, rmx;
-                        bool rhave;
-                        fold_range(gstream, bd->field_enc, bd->field_first,
-                                   bd->field_len, n, aa, bb2,
-                                   EN_VALUES && (flags & KF_NEED_VALUES), lane,
-                                   &rsum, &rmn, &rmx, &rhave, &rcnt,
-                                   plain_norm, raw_f64, derr, (uint64_t)bi,
-                                   bw0, bw1, bw2);
-                        double rfs = 1.0;
-                        if ((flags & KF_FLOAT) && fdiff) {
-                            int64_t mfac = c_pow10i[fdiff];
-                            rfs = (double)mfac;
-                            if (rhave) {
-                                int64_t smin, smax;
-                                if (__builtin_mul_overflow(rmn, mfac, &smin) ||
-                                    __builtin_mul_overflow(rmx, mfac, &smax)) {
-                                    dev_set_err(derr, DERR_EXP_MISMATCH,
-                                                (uint64_t)bi);
-                                    rhave = false;
-                                } else {
-                                    rmn = smin;
-                                    rmx = smax;
-                                }
-                            }
-                        }
-                        if (comp != cur_group) {
-                            flush_partial(partials, cur_group, wsum, wcnt,
-                                          wmin, wmax, wsumf, lane,
-                                          first_seen, wfirst);
-                            cur_group = comp;
-                            wsum = 0; wcnt = 0; wmin = INT64_MAX;
-                            wmax = INT64_MIN; wsumf = 0;
-                            wfirst = ((uint64_t)wi << 13) | (uint64_t)aa;
-                        } else if (wfirst == ~0ull) {
-                            wfirst = ((uint64_t)wi << 13) | (uint64_t)aa;
-                        }
-                        wsum += rsum;
-                        wcnt += rcnt;
-                        if (rhave) {
-                            wmin = rmn < wmin ? rmn : wmin;
-                            wmax = rmx > wmax ? rmx : wmax;
-                        }
-                        if (flags & KF_FLOAT) {
-                            if (raw_f64) {
-                                double db;
-                                uint64_t ub = rsum;
-                                __builtin_memcpy(&db, &ub, 8);
-                                wsumf += db;
-                            } else {
-                                wsumf += (double)(int64_t)rsum * rfs;
-                            }
-                        }
+                        RowFold rf;
+                        fold_range(
+                            gstream, plain_norm, bd->field_enc,
+                            bd->field_first, bd->field_len, n, aa, bb2,
+                            EN_VALUES && (flags & KF_NEED_VALUES), raw_f64,
+                            lane, bw0, bw1, bw2, derr, (uint64_t)bi, &rf);
+                        part.add(comp, ((uint64_t)wi << 13) | (uint64_t)aa, rf,
+                                 flags, fdiff, raw_f64, false, partials,
+                                 first_seen, lane, derr, (uint64_t)bi);
                     }
                     for (int sl = 0; sl < n_gslots; sl++)
                         if (run_hi_s[sl] == hi && gb[sl].uniform_gid == GID_VARYING)
@@ -3373,365 +3396,81 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
         const uint8_t fenc = bd->field_enc;
         const int64_t first = bd->field_first;
         const uint8_t *fstream = payload + bd->field_off;
-        uint64_t bsum = 0;          // block sum (wrapping)
-        int64_t bmin = INT64_MAX, bmax = INT64_MIN;
-        bool have_minmax = false;
-
-        uint64_t nsel_eff = nsel;
-        if (pred_on && (fenc == BYDB_ENC_CONST || fenc == BYDB_ENC_DELTA_CONST)) {
-            int64_t dd = 0;
-            if (fenc == BYDB_ENC_DELTA_CONST) {
-                int vl;
-                dd = decode_one_varint(fstream, &vl);
-            }
-            uint64_t psum, pcnt;
-            fold_arith_pred(first, dd, r0, r1, lane, wp0, wp1, wp2, &psum,
-                            &pcnt, &bmin, &bmax);
-            bsum = lane == 0 ? psum : 0;
-            nsel_eff = pcnt;
-            have_minmax = (EN_VALUES && (flags & KF_NEED_VALUES)) && pcnt > 0;
-        } else if (pred_on &&
-                   (fenc == BYDB_ENC_DELTA || fenc == BYDB_ENC_DELTA_OF_DELTA)) {
-            bool dod = fenc == BYDB_ENC_DELTA_OF_DELTA;
-            const uint8_t *s = fstream;
-            int64_t d1 = 0;
-            if (dod) {
-                int vl;
-                d1 = decode_one_varint(s, &vl);
-                s += vl;
-            }
-            int64_t row1 = (int64_t)((uint64_t)first + (uint64_t)d1);
-            // rows outside the stream first (walker rows must ascend)
+        RowFold bf;
+        if (use_seg) {
+            const bool dod = fenc == BYDB_ENC_DELTA_OF_DELTA;
+            // (SegEntry preloaded at item start)
+            // segment-parallel value scan: this wave folds only rows
+            // [seg*SEG_ROWS+1 .. min((seg+1)*SEG_ROWS, n-1)] (+ rows 0
+            // and, for delta-of-delta, 1 on segment 0), starting from
+            // the indexed byte offset and carries — no cross-segment
+            // dependency.  For delta-of-delta, segment k >= 1 relabels
+            // absolute row (k*SEG_ROWS - 1 + j'), so j' = 2 lands on
+            // the segment's first row and e.v_start/e.d1_start are the
+            // carries at row k*SEG_ROWS.
+            const SegEntry e = e_pre;
+            int64_t sj_lo = (int64_t)seg * SEG_ROWS + 1;
+            int64_t sj_hi = ((int64_t)seg + 1) * SEG_ROWS;
+            if (sj_hi > n - 1) sj_hi = n - 1;
+            int64_t a = sj_lo > r0 ? sj_lo : r0;
+            int64_t b = sj_hi < r1 ? sj_hi : r1;
+            bool handle0 = seg == 0 && r0 <= 0 && 0 <= r1;
+            bool handle1 = dod && seg == 0 && r0 <= 1 && 1 <= r1;
+            if (dod && seg == 0 && a < 2) a = 2;
+            if (a > b && !handle0 && !handle1) continue;
             uint64_t lsum = 0, lcnt = 0;
             int64_t lmn = INT64_MAX, lmx = INT64_MIN;
-            bool need0 = lane == 0 && r0 <= 0 && 0 <= r1;
-            bool m0 = true;
-            if (wp0) m0 = pred_match_rows(wp0, 0, need0 && m0) && m0;
-            if (wp1) m0 = pred_match_rows(wp1, 0, need0 && m0) && m0;
-            if (wp2) m0 = pred_match_rows(wp2, 0, need0 && m0) && m0;
-            if (need0 && m0) { lsum += (uint64_t)first; lcnt++;
-                lmn = first; lmx = first; }
-            if (dod) {
-                bool need1 = lane == 0 && r0 <= 1 && 1 <= r1;
-                bool m1 = true;
-                if (wp0) m1 = pred_match_rows(wp0, 1, need1 && m1) && m1;
-                if (wp1) m1 = pred_match_rows(wp1, 1, need1 && m1) && m1;
-                if (wp2) m1 = pred_match_rows(wp2, 1, need1 && m1) && m1;
-                if (need1 && m1) { lsum += (uint64_t)row1; lcnt++;
-                    lmn = row1 < lmn ? row1 : lmn; lmx = row1 > lmx ? row1 : lmx; }
-            }
-            ScanFold ff;
-            scan_stream(s, n - 1, dod, dod ? row1 : first, d1, r0, r1,
-                        lane, &ff, derr, (uint64_t)bi, wp0, wp1, wp2,
-                        !EN_CLAMP);
-            lsum += ff.sum;
-            lcnt += ff.nsel;
-            lmn = ff.mn < lmn ? ff.mn : lmn;
-            lmx = ff.mx > lmx ? ff.mx : lmx;
-            bsum = wave_reduce_add(lsum);
-            nsel_eff = wave_reduce_add(lcnt);
-            bmin = wave_reduce_min(lmn);
-            bmax = wave_reduce_max(lmx);
-            have_minmax = nsel_eff > 0;
-            bsum = lane == 0 ? bsum : 0;
-        } else if (fenc == BYDB_ENC_CONST) {
-            if (lane == 0) bsum = (uint64_t)first * nsel;
-            bmin = bmax = first;
-            have_minmax = true;
-        } else if (fenc == BYDB_ENC_DELTA_CONST) {
-            int vl;
-            int64_t dd = decode_one_varint(fstream, &vl);
-            if (lane == 0) {
-                // sum_{i=r0..r1}(first + i*dd) = nsel*first + dd * sum i
-                uint64_t si = (uint64_t)(r0 + r1) * nsel / 2;
-                bsum = (uint64_t)first * nsel + (uint64_t)dd * si;
-            }
-            if (EN_VALUES && (flags & KF_NEED_VALUES)) {
-                // reconstruct min/max exactly (wrap-safe): walk rows by lanes
-                int64_t lmn = INT64_MAX, lmx = INT64_MIN;
-                for (int64_t base = r0; base <= r1; base += WAVE) {
-                    int64_t i = base + lane;
-                    if (i <= r1) {
-                        int64_t v = (int64_t)((uint64_t)first + (uint64_t)i * (uint64_t)dd);
-                        lmn = v < lmn ? v : lmn;
-                        lmx = v > lmx ? v : lmx;
-                    }
-                }
-                bmin = wave_reduce_min(lmn);
-                bmax = wave_reduce_max(lmx);
-                have_minmax = true;
-            }
-        } else if (fenc == BYDB_ENC_DELTA || fenc == BYDB_ENC_DELTA_OF_DELTA) {
-            bool dod = fenc == BYDB_ENC_DELTA_OF_DELTA;
-            if (!(EN_VALUES && (flags & KF_NEED_VALUES))) {
-                uint64_t acc;
-                if (!dod) {
-                    if (bd->field_len == (uint64_t)(n - 1)) {
-                        // stream length == delta count -> every varint is
-                        // one byte: dense dot4 fold, inlined with the whole
-                        // block in flight in the closed-form instantiations
-                        acc = !UNI_DESC
-                                  ? dense_delta_weighted(fstream, n - 1, r0,
-                                                         r1, lane)
-                                  : dense_delta_weighted_t<EN_CLAMP ? DENSE_CHUNKS_CLAMP : DENSE_CHUNKS_BLOCK, EN_STREAM>(
-                                        fstream, n - 1, r0, r1, lane);
-                    } else {
-                        acc = fold_delta_weighted_fast(fstream, n - 1, r0, r1,
-                                                       lane, derr,
-                                                       (uint64_t)bi);
-                    }
-                    acc = wave_reduce_add(acc);
-                    if (lane == 0) {
-                        bsum = (uint64_t)first * nsel + acc;
-                    }
-                } else {
-                    int vl;
-                    int64_t d1 = decode_one_varint(fstream, &vl);
-                    acc = fold_dod_weighted(fstream + vl, n - 1, r0, r1, lane,
-                                            derr, (uint64_t)bi);
-                    acc = wave_reduce_add(acc);
-                    if (lane == 0) {
-                        // nsel*first + d1 * sum_{i=r0..r1} i + weighted d2
-                        uint64_t si = (uint64_t)(r0 + r1) * nsel / 2;
-                        bsum = (uint64_t)first * nsel + (uint64_t)d1 * si + acc;
-                    }
-                }
-            } else if (use_seg) {
-                // (SegEntry preloaded at item start)
-                // segment-parallel value scan: this wave folds only rows
-                // [seg*SEG_ROWS+1 .. min((seg+1)*SEG_ROWS, n-1)] (+ rows 0
-                // and, for delta-of-delta, 1 on segment 0), starting from
-                // the indexed byte offset and carries — no cross-segment
-                // dependency.  For delta-of-delta, segment k >= 1 relabels
-                // absolute row (k*SEG_ROWS - 1 + j'), so j' = 2 lands on
-                // the segment's first row and e.v_start/e.d1_start are the
-                // carries at row k*SEG_ROWS.
-                const SegEntry e = e_pre;
-                int64_t sj_lo = (int64_t)seg * SEG_ROWS + 1;
-                int64_t sj_hi = ((int64_t)seg + 1) * SEG_ROWS;
-                if (sj_hi > n - 1) sj_hi = n - 1;
-                int64_t a = sj_lo > r0 ? sj_lo : r0;
-                int64_t b = sj_hi < r1 ? sj_hi : r1;
-                bool handle0 = seg == 0 && r0 <= 0 && 0 <= r1;
-                bool handle1 = dod && seg == 0 && r0 <= 1 && 1 <= r1;
-                if (dod && seg == 0 && a < 2) a = 2;
-                if (a > b && !handle0 && !handle1) continue;
-                uint64_t lsum = 0, lcnt = 0;
-                int64_t lmn = INT64_MAX, lmx = INT64_MIN;
-                if (a <= b) {
-                    ScanFold ff;
-                    int64_t rel0 = dod ? ((int64_t)seg * SEG_ROWS -
-                                          (seg ? 1 : 0))
-                                       : (int64_t)seg * SEG_ROWS;
-                    scan_stream(fstream + e.byte_off, b - rel0, dod,
-                                e.v_start, e.d1_start, a - rel0, b - rel0,
-                                lane, &ff, derr, (uint64_t)bi, nullptr,
-                                nullptr, nullptr, !EN_CLAMP);
-                    lsum = ff.sum;
-                    lcnt = ff.nsel;
-                    lmn = ff.mn;
-                    lmx = ff.mx;
-                }
-                if (lane == 0 && handle0) {
-                    lsum += (uint64_t)first;
-                    lcnt++;
-                    lmn = first < lmn ? first : lmn;
-                    lmx = first > lmx ? first : lmx;
-                }
-                if (lane == 0 && handle1) {
-                    int64_t row1 = e.v_start;  // seg 0: v at row 1
-                    lsum += (uint64_t)row1;
-                    lcnt++;
-                    lmn = row1 < lmn ? row1 : lmn;
-                    lmx = row1 > lmx ? row1 : lmx;
-                }
-                bsum = wave_reduce_add(lsum);
-                nsel_eff = wave_reduce_add(lcnt);
-                bmin = wave_reduce_min(lmn);
-                bmax = wave_reduce_max(lmx);
-                have_minmax = nsel_eff > 0;
-                bsum = lane == 0 ? bsum : 0;
-            } else if (!dod && bd->field_len == (uint64_t)(n - 1)) {
-                // all-1-byte delta stream: dense weighted sum + dense
-                // min/max (no serial window chain)
-                uint64_t acc = dense_delta_weighted(fstream, n - 1, r0, r1,
-                                                    lane);
-                acc = wave_reduce_add(acc);
-                bsum = (uint64_t)first * nsel + acc;
-                bsum = lane == 0 ? bsum : 0;
-                // v at delta index r0 (v_{r0}) = first + sum of bytes [0,r0)
-                int64_t psd, psjd;
-                dense_region(fstream, 0, r0, lane, &psd, &psjd);
-                int64_t vr0 = (int64_t)((uint64_t)first +
-                                        wave_reduce_add((uint64_t)psd));
-                dense_minmax(fstream, r0, r1, vr0, lane, &bmin, &bmax);
-                bmin = vr0 < bmin ? vr0 : bmin;  // row r0 itself
-                bmax = vr0 > bmax ? vr0 : bmax;
-                have_minmax = true;
-            } else {
-                const uint8_t *s = fstream;
-                int64_t d1 = 0;
-                if (dod) {
-                    int vl;
-                    d1 = decode_one_varint(s, &vl);
-                    s += vl;
-                }
-                int64_t row1 = (int64_t)((uint64_t)first + (uint64_t)d1);
+            if (a <= b) {
                 ScanFold ff;
-                scan_stream(s, n - 1, dod, dod ? row1 : first, d1, r0, r1,
-                            lane, &ff, derr, (uint64_t)bi, nullptr, nullptr,
-                            nullptr, !EN_CLAMP);
-                uint64_t lsum = ff.sum;
-                int64_t lmn = ff.mn, lmx = ff.mx;
-                // rows outside the stream: row 0 (value=first) and, for
-                // dod, row 1 (value=row1)
-                if (lane == 0) {
-                    if (r0 <= 0 && 0 <= r1) {
-                        lsum += (uint64_t)first;
-                        lmn = first < lmn ? first : lmn;
-                        lmx = first > lmx ? first : lmx;
-                    }
-                    if (dod && r0 <= 1 && 1 <= r1) {
-                        lsum += (uint64_t)row1;
-                        lmn = row1 < lmn ? row1 : lmn;
-                        lmx = row1 > lmx ? row1 : lmx;
-                    }
-                }
-                bsum = wave_reduce_add(lsum);
-                bmin = wave_reduce_min(lmn);
-                bmax = wave_reduce_max(lmx);
-                have_minmax = true;
+                int64_t rel0 = dod ? ((int64_t)seg * SEG_ROWS -
+                                      (seg ? 1 : 0))
+                                   : (int64_t)seg * SEG_ROWS;
+                scan_stream(fstream + e.byte_off, b - rel0, dod,
+                            e.v_start, e.d1_start, a - rel0, b - rel0,
+                            lane, &ff, derr, (uint64_t)bi, nullptr,
+                            nullptr, nullptr, !EN_CLAMP);
+                lsum = ff.sum;
+                lcnt = ff.nsel;
+                lmn = ff.mn;
+                lmx = ff.mx;
             }
-        } else if (fenc == BYDB_ENC_PLAIN) {
-            // null-bearing Plain column, host-normalized into the sidecar
-            // ([u32 n][pad][validity bitmap][8-B sign-flip cells]): fold
-            // valid selected rows, decoding cells in-lane
-            // (convert/number.go:95-108); nulls drop from count and every
-            // aggregate (aggregation.go:310).
-            if (!(bd->field_off & TAG_SIDECAR_BIT)) {
-                dev_set_err(derr, DERR_BAD_ENC, (uint64_t)bi);
-                continue;
+            if (lane == 0 && handle0) {
+                lsum += (uint64_t)first;
+                lcnt++;
+                lmn = first < lmn ? first : lmn;
+                lmx = first > lmx ? first : lmx;
             }
-            const uint8_t *fp = sidecar + (bd->field_off & ~TAG_SIDECAR_BIT);
-            uint32_t nn = (uint32_t)fp[0] | ((uint32_t)fp[1] << 8) |
-                          ((uint32_t)fp[2] << 16) | ((uint32_t)fp[3] << 24);
-            if (nn != (uint32_t)n) {
-                dev_set_err(derr, DERR_BAD_ENC, (uint64_t)bi);
-                continue;
+            if (lane == 0 && handle1) {
+                int64_t row1 = e.v_start;  // seg 0: v at row 1
+                lsum += (uint64_t)row1;
+                lcnt++;
+                lmn = row1 < lmn ? row1 : lmn;
+                lmx = row1 > lmx ? row1 : lmx;
             }
-            const uint64_t *vbm = (const uint64_t *)(fp + 8);
-            const uint64_t *cells = vbm + ((uint64_t)nn + 63) / 64;
-            uint64_t lsum = 0, lcnt = 0;
-            double lsumf = 0.0;
-            int64_t lmn = INT64_MAX, lmx = INT64_MIN;
-            for (int64_t base = r0; base <= r1; base += WAVE) {
-                int64_t row = base + lane;
-                bool ok = row <= r1 &&
-                          ((vbm[row >> 6] >> (row & 63)) & 1);
-                if (wp0) ok = pred_match_rows(wp0, row, ok) && ok;
-                if (wp1) ok = pred_match_rows(wp1, row, ok) && ok;
-                if (wp2) ok = pred_match_rows(wp2, row, ok) && ok;
-                if (ok) {
-                    uint64_t c = cells[row];
-                    // cells are big-endian on the wire
-                    uint64_t u = __builtin_bswap64(c);
-                    if (raw_f64) {
-                        // IEEE-754 bits: double sum + ordered-bits
-                        // min/max (Float64ToOrderedBytes map,
-                        // convert/number.go:148-157)
-                        double dv;
-                        __builtin_memcpy(&dv, &u, 8);
-                        lsumf += dv;
-                        // order-preserving map INTO THE SIGNED domain
-                        // (min/max compare as int64): positives keep raw
-                        // bits, negatives flip magnitude and sign
-                        int64_t kv =
-                            (u >> 63)
-                                ? (int64_t)(~u ^ 0x8000000000000000ull)
-                                : (int64_t)u;
-                        lmn = kv < lmn ? kv : lmn;
-                        lmx = kv > lmx ? kv : lmx;
-                    } else {
-                        int64_t v = (u >> 63)
-                                        ? (int64_t)(u & ~(1ull << 63))
-                                        : -(int64_t)((1ull << 63) - u);
-                        lsum += (uint64_t)v;
-                        lmn = v < lmn ? v : lmn;
-                        lmx = v > lmx ? v : lmx;
-                    }
-                    lcnt++;
-                }
-            }
-            if (raw_f64) {
-                double ds = wave_reduce_addf(lsumf);
-                uint64_t db;
-                __builtin_memcpy(&db, &ds, 8);
-                bsum = lane == 0 ? db : 0;
-            } else {
-                bsum = wave_reduce_add(lsum);
-                bsum = lane == 0 ? bsum : 0;
-            }
-            nsel_eff = wave_reduce_add(lcnt);
-            bmin = wave_reduce_min(lmn);
-            bmax = wave_reduce_max(lmx);
-            have_minmax = nsel_eff > 0;
+            bf.sum = wave_reduce_add(lsum);
+            bf.cnt = wave_reduce_add(lcnt);
+            bf.mn = wave_reduce_min(lmn);
+            bf.mx = wave_reduce_max(lmx);
+            bf.have_mm = bf.cnt > 0;
         } else {
-            dev_set_err(derr, DERR_BAD_ENC, (uint64_t)bi);
-            continue;
+            const uint8_t *plain_norm =
+                (fenc == BYDB_ENC_PLAIN && (bd->field_off & TAG_SIDECAR_BIT))
+                    ? sidecar + (bd->field_off & ~TAG_SIDECAR_BIT)
+                    : nullptr;
+            bf = fold_rows<EN_VALUES, !EN_CLAMP,
+                           !UNI_DESC ? DENSE_CALL
+                                     : EN_STREAM ? DENSE_INLINE_NT
+                                                 : DENSE_INLINE>(
+                fstream, plain_norm, fenc, first, bd->field_len, n, r0, r1,
+                (flags & KF_NEED_VALUES) != 0, raw_f64, lane, wp0, wp1, wp2,
+                derr, (uint64_t)bi);
         }
-
-        // rows 0 (+1 for dod) fast path bookkeeping: the weighted folds
-        // above already include first (and d1) in their closed forms.
-
-        // ---- accumulate into the per-wave register partial ----
-        // One atomic set per BLOCK on a single group serialises on one
-        // cacheline (~88 atomics/us on one word) and dominates the whole
-        // scan; instead fold block totals into per-wave registers and
-        // flush only when the group changes or the wave is done.
-        bsum = (uint64_t)__shfl((long long)bsum, 0);  // lane0 holds closed forms
-        double fscale = 1.0;
-        if ((flags & KF_FLOAT) && fdiff) {
-            int64_t mfac = c_pow10i[fdiff];
-            fscale = (double)mfac;
-            if (have_minmax) {
-                int64_t smin, smax;
-                if (__builtin_mul_overflow(bmin, mfac, &smin) ||
-                    __builtin_mul_overflow(bmax, mfac, &smax)) {
-                    dev_set_err(derr, DERR_EXP_MISMATCH, (uint64_t)bi);
-                    continue;
-                }
-                bmin = smin;
-                bmax = smax;
-            }
-        }
-        if (block_group != cur_group) {
-            flush_partial(partials, cur_group, wsum, wcnt, wmin, wmax, wsumf,
-                          lane, first_seen, wfirst);
-            cur_group = block_group;
-            wsum = 0; wcnt = 0; wmin = INT64_MAX; wmax = INT64_MIN; wsumf = 0;
-            wfirst = ((uint64_t)wi << 13) | (uint64_t)r0;
-        } else if (wfirst == ~0ull) {
-            wfirst = ((uint64_t)wi << 13) | (uint64_t)r0;
-        }
-        wsum += bsum;
-        wcnt += nsel_eff;
-        if (have_minmax) {
-            wmin = bmin < wmin ? bmin : wmin;
-            wmax = bmax > wmax ? bmax : wmax;
-        }
-        if (flags & KF_FLOAT) {
-            if (raw_f64) {
-                double db;
-                uint64_t ub = bsum;
-                __builtin_memcpy(&db, &ub, 8);
-                wsumf += db;
-            } else {
-                wsumf += (double)(int64_t)bsum * fscale;
-            }
-        }
+        // a rescale overflow drops the block
+        part.add(block_group, ((uint64_t)wi << 13) | (uint64_t)r0, bf, flags,
+                 fdiff, raw_f64, true, partials, first_seen, lane, derr,
+                 (uint64_t)bi);
     }
-    flush_partial(partials, cur_group, wsum, wcnt, wmin, wmax, wsumf, lane,
-                  first_seen, wfirst);
+    part.flush(partials, first_seen, lane);
 }
 
 // ---------------- cross-part version dedup ----------------
@@ -4805,19 +4544,8 @@ static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
     const bool en_values = (flags & KF_NEED_VALUES) != 0;
     const bool en_preds = n_preds > 0;
     const bool en_groups = groups != nullptr;
-    void (*kfn)(const uint8_t *, const uint8_t *, const bydb_block_desc *,
-                int64_t, int64_t, int64_t, int, const PredBlock *, int,
-                const uint64_t *, const uint8_t *, const SegEntry *,
-                const GroupBlock *, const uint16_t *, const uint16_t *, int,
-                int64_t, int64_t, int64_t, int64_t, bydb_partial *,
-                DevErr *, const uint32_t *, uint64_t *);
-    void (*kfn_walk)(const uint8_t *, const uint8_t *,
-                     const bydb_block_desc *, int64_t, int64_t, int64_t, int,
-                     const PredBlock *, int, const uint64_t *,
-                     const uint8_t *, const SegEntry *, const GroupBlock *,
-                     const uint16_t *, const uint16_t *, int, int64_t,
-                     int64_t, int64_t, int64_t, bydb_partial *, DevErr *,
-                     const uint32_t *, uint64_t *) = nullptr;
+    using ScanFn = decltype(&k_scan_agg_t<false, false, false, false, false>);
+    ScanFn kfn, kfn_walk = nullptr;
     // the clamp-free instantiations run when the query range covers the
     // whole resident part (the common analytic scan; per-block FindRange
     // is then an identity)
@@ -4859,29 +4587,24 @@ static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
         kfn = en_clamp
                   ? k_scan_agg_t<false, false, false, false, true, true>
                   : k_scan_agg_t<false, false, false, false, false, true>;
-    // light pass: every block whose predicate verdict is uniform (no
-    // walker state, no scratch spills in the scan loop)
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(threads), 0, s->stream,
-                       s->d_payload, s->d_sidecar, s->d_blocks, s->n_blocks,
-                       min_ts, max_ts, flags, preds, n_preds, s->d_pred_bm,
-                       s->d_pred_flags, segs, groups, s->d_gmap, s->d_gruns,
-                       s->n_gslots, s->gmul[0], s->gmul[1], s->gmul[2],
-                       (int64_t)s->n_groups, s->d_acc, s->d_err, nullptr,
-                       s->d_first_seen);
-    HIP_TRY(s, hipGetLastError());
-    // heavy pass: only the PF_WALK blocks (row-varying predicates).  When
-    // none exist this is a flag-byte sweep (~tens of us)
-    if (kfn_walk != nullptr) {
-        hipLaunchKernelGGL(kfn_walk, dim3(grid), dim3(threads), 0, s->stream,
+    auto launch = [&](ScanFn fn, int pass_flags, const uint32_t *walk_count) {
+        hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), 0, s->stream,
                            s->d_payload, s->d_sidecar, s->d_blocks,
-                           s->n_blocks, min_ts, max_ts, flags | KF_WALK_ONLY,
-                           preds, n_preds, s->d_pred_bm, s->d_pred_flags,
-                           segs, groups, s->d_gmap, s->d_gruns, s->n_gslots,
+                           s->n_blocks, min_ts, max_ts, pass_flags, preds,
+                           n_preds, s->d_pred_bm, s->d_pred_flags, segs,
+                           groups, s->d_gmap, s->d_gruns, s->n_gslots,
                            s->gmul[0], s->gmul[1], s->gmul[2],
                            (int64_t)s->n_groups, s->d_acc, s->d_err,
-                           s->d_walk_count, s->d_first_seen);
-        HIP_TRY(s, hipGetLastError());
-    }
+                           walk_count, s->d_first_seen);
+        return hipGetLastError();
+    };
+    // light pass: every block whose predicate verdict is uniform (no
+    // walker state, no scratch spills in the scan loop)
+    HIP_TRY(s, launch(kfn, flags, nullptr));
+    // heavy pass: only the PF_WALK blocks (row-varying predicates).  When
+    // none exist this is a flag-byte sweep (~tens of us)
+    if (kfn_walk != nullptr)
+        HIP_TRY(s, launch(kfn_walk, flags | KF_WALK_ONLY, s->d_walk_count));
     HIP_TRY(s, hipEventRecord(s->ev_stop, s->stream));
     s->consumed = true;
     return BYDB_OK;
