@@ -563,6 +563,24 @@ __device__ uint64_t dense_delta_weighted(const uint8_t *stream,
                                                             r0, r1, lane);
 }
 
+// The delta that ends at a terminator lane of the 64-byte window at `win`
+// (b: the lane's own byte), for windows that START on a varint: the groups
+// below the terminator are re-read from memory.
+__device__ __forceinline__ int64_t varint_reread(const uint8_t *win,
+                                                 uint64_t emask, uint8_t b,
+                                                 int lane) {
+    uint64_t below = emask & lanemask_lt(lane);
+    int start = below ? (64 - __clzll(below)) : 0;
+    uint64_t u = 0;
+    unsigned sh = 0;
+    for (int i = start; i < lane; ++i) {
+        u |= (uint64_t)(win[i] & 0x7f) << sh;
+        sh += 7;
+    }
+    u |= (uint64_t)b << sh;
+    return zz_dec(u);
+}
+
 // Fast weighted delta fold: 256-byte windows (one dword per lane) with an
 // all-1-byte fast case — the dominant shape for delta-encoded telemetry
 // (zigzag deltas < 64 encode to one byte, int.go:84-88).  For a window
@@ -669,16 +687,7 @@ __device__ __forceinline__ uint64_t fold_delta_weighted_fast(const uint8_t *stre
             if (emask == ~0ull) {
                 d = zz_dec(b);
             } else if (is_term) {
-                uint64_t below = emask & lanemask_lt(lane);
-                int start = below ? (64 - __clzll(below)) : 0;
-                uint64_t u = 0;
-                unsigned sh = 0;
-                for (int i = start; i < lane; ++i) {
-                    u |= (uint64_t)(stream[pos + (uint64_t)i] & 0x7f) << sh;
-                    sh += 7;
-                }
-                u |= (uint64_t)b << sh;
-                d = zz_dec(u);
+                d = varint_reread(stream + pos, emask, b, lane);
             } else {
                 d = 0;
             }
@@ -720,16 +729,7 @@ __device__ __forceinline__ uint64_t fold_dod_weighted(const uint8_t *stream, int
         if (emask == ~0ull) {
             d = zz_dec(b);
         } else if (is_term) {
-            uint64_t below = emask & lanemask_lt(lane);
-            int start = below ? (64 - __clzll(below)) : 0;
-            uint64_t u = 0;
-            unsigned sh = 0;
-            for (int i = start; i < lane; ++i) {
-                u |= (uint64_t)(stream[pos + (uint64_t)i] & 0x7f) << sh;
-                sh += 7;
-            }
-            u |= (uint64_t)b << sh;
-            d = zz_dec(u);
+            d = varint_reread(stream + pos, emask, b, lane);
         } else {
             d = 0;
         }
@@ -1991,14 +1991,15 @@ __device__ void scan_stream(const uint8_t *stream, int64_t n_deltas, bool dod,
     // Fixed-size window advance with a cross-window varint carry
     // (carry_u holds the carried low groups, carry_n its byte count), so
     // window addresses are induction variables.  The primary window is
-    // 128 B with TWO bytes per lane (one u16 load): when every varint is
+    // 256 B with FOUR bytes per lane (one u32 load): when every varint is
     // 1-2 bytes — the dominant telemetry shape — each lane decodes up to
-    // two values and one 32-bit scan covers 128 B, halving per-byte
-    // instruction and load counts vs the 64-B window.  Windows that fail
-    // the pattern (longer varints, walkers, the stream tail, a multi-byte
-    // carry) fall back to the 64-B machinery below.  Terminators past
-    // jmax (bytes of the following stream / the part's 1-KiB slack) fold
-    // as zeros, so the wave-wide scans read their totals at lane 63.
+    // four values and one 32-bit scan covers 256 B, a quarter of the 64-B
+    // window's per-byte instruction and load counts.  Windows that fail
+    // the pattern (longer varints, walkers, delta-of-delta, the stream
+    // tail, a multi-byte carry) take one 64-B window below: its 1-2-byte
+    // fast shape, or the generic step.  Terminators past jmax (bytes of
+    // the following stream / the part's slack) fold as zeros, so the
+    // wave-wide scans read their totals at lane 63.
     uint64_t carry_u = 0;
     uint32_t carry_n = 0;
     const bool no_walk = pw0 == nullptr && pw1 == nullptr && pw2 == nullptr;
@@ -2203,6 +2204,10 @@ __device__ void scan_stream(const uint8_t *stream, int64_t n_deltas, bool dod,
             pos += 64;
             continue;
         }
+        // The generic step.  clamp_count_stream and dedup_decode_stream
+        // hold the same lines from here to the carry-out: a codec fix goes
+        // into all three (why they are not one routine yet:
+        // profiles/varint_walk.txt).
         uint64_t d = 0;
         if (emask == ~0ull && carry_n == 0) {
             d = (uint64_t)zz_dec(b);
@@ -2386,230 +2391,6 @@ __device__ void clamp_count_stream(
     }
     *out_nlo = wave_reduce_add(l_nlo);
     *out_nhi = wave_reduce_add(l_nhi);
-}
-
-// ---------------- varint segment index ----------------
-// The value-reconstruction path over a mixed-width varint stream is a
-// serial chain of ballot windows (the next window's address depends on the
-// current ballot).  For a RESIDENT part that chain can be broken once:
-// a build pass walks each eligible stream and records, every SEG_ROWS
-// values, the byte offset and running value at the segment start.  The
-// scan then processes (block, segment) pairs independently — 8x more
-// parallel units and no cross-segment dependency.  The index is built
-// once per part upload + agg shape (like the reference's block metadata,
-// it is derived state over immutable part bytes).
-#define SEG_ROWS 8192
-#define MAX_SEGS 1
-#define SEG_INELIGIBLE 0xFFFFFFFFu
-
-struct SegEntry {
-    uint32_t byte_off;   // offset of the segment's first delta in the stream
-    uint32_t _pad;
-    int64_t v_start;     // value at row seg*SEG_ROWS (before the first delta)
-    int64_t d1_start;    // delta-of-delta streams: d1 at row seg*SEG_ROWS
-};
-
-__global__ __launch_bounds__(256) void k_build_seg_index(
-    const uint8_t *__restrict__ payload, const bydb_block_desc *__restrict__ blocks,
-    int64_t n_blocks, SegEntry *__restrict__ segs, DevErr *derr) {
-    const int lane = threadIdx.x & 63;
-    int64_t wave_id = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    int64_t n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t bi = wave_id; bi < n_blocks; bi += n_waves) {
-        const bydb_block_desc *bd = &blocks[bi];
-        SegEntry *bseg = segs + bi * MAX_SEGS;
-        const int64_t n = (int64_t)bd->count;
-        const bool dod = bd->field_enc == BYDB_ENC_DELTA_OF_DELTA;
-        bool eligible =
-            n > SEG_ROWS &&
-            ((bd->field_enc == BYDB_ENC_DELTA &&
-              bd->field_len != (uint64_t)(n - 1)) ||
-             dod);
-        if (!eligible) {
-            if (lane == 0) bseg[0].byte_off = SEG_INELIGIBLE;
-            continue;
-        }
-        const uint8_t *stream = payload + bd->field_off;
-        uint64_t d2_off = 0;
-        uint64_t d1_carry = 0;
-        if (dod) {
-            int vl;
-            d1_carry = (uint64_t)decode_one_varint(stream, &vl);
-            d2_off = (uint64_t)vl;
-        }
-        if (lane == 0) {
-            bseg[0].byte_off = (uint32_t)d2_off;
-            bseg[0].v_start =
-                dod ? (int64_t)((uint64_t)bd->field_first + d1_carry)
-                    : bd->field_first;
-            bseg[0].d1_start = (int64_t)d1_carry;
-        }
-        const uint8_t *d2s = stream + d2_off;
-        const int64_t n_deltas = n - 1 - (dod ? 1 : 0);
-        // j here indexes the per-stream varint: absolute row = j (delta)
-        // or j + 1 (delta-of-delta)
-        uint64_t pos = 0;
-        int64_t j = 1;
-        uint64_t v_carry = (uint64_t)bd->field_first + (dod ? d1_carry : 0);
-        // delta streams walk 128-B paired-lane windows (the scan_stream
-        // fast shape) and record boundaries per value; non-qualifying
-        // windows rewind any carried byte and use the 64-B machinery
-        uint64_t carry_u2 = 0;
-        uint32_t carry_n2 = 0;
-        while (j <= n_deltas) {
-            if (!dod && carry_n2 <= 1) {
-                uint16_t pr;
-                __builtin_memcpy(&pr, d2s + pos + 2 * (uint64_t)lane, 2);
-                uint32_t b0 = pr & 0xffu, b1 = (uint32_t)pr >> 8;
-                uint64_t e0 = __ballot(b0 < 0x80);
-                uint64_t e1 = __ballot(b1 < 0x80);
-                uint64_t c0 = ~e0, c1 = ~e1;
-                int nt = __popcll(e0) + __popcll(e1);
-                if ((c0 & c1) == 0 && (c1 & (c0 >> 1)) == 0 &&
-                    (int64_t)nt <= n_deltas - j + 1 &&
-                    (carry_n2 == 0 || (e0 & 1))) {
-                    uint32_t pb1 = dpp_mov32<0x111>(b1);
-                    uint32_t q15 =
-                        (uint32_t)__builtin_amdgcn_readlane((int)b1, 15);
-                    uint32_t q31 =
-                        (uint32_t)__builtin_amdgcn_readlane((int)b1, 31);
-                    uint32_t q47 =
-                        (uint32_t)__builtin_amdgcn_readlane((int)b1, 47);
-                    if ((lane & 15) == 0 && lane)
-                        pb1 = lane == 16 ? q15 : lane == 32 ? q31 : q47;
-                    if (lane == 0)
-                        pb1 = carry_n2 ? ((uint32_t)carry_u2 | 0x80u) : 0;
-                    bool t0 = b0 < 0x80, t1 = b1 < 0x80;
-                    uint32_t u0 =
-                        (pb1 & 0x80u) ? ((pb1 & 0x7fu) | (b0 << 7)) : b0;
-                    uint32_t u1 =
-                        (b0 & 0x80u) ? ((b0 & 0x7fu) | (b1 << 7)) : b1;
-                    int32_t dA =
-                        t0 ? ((int32_t)(u0 >> 1) ^ -(int32_t)(u0 & 1)) : 0;
-                    int32_t dB =
-                        t1 ? ((int32_t)(u1 >> 1) ^ -(int32_t)(u1 & 1)) : 0;
-                    int32_t sl = dA + dB;
-                    int32_t S = wave_incl_scan32(sl, lane);
-                    int32_t pre = S - sl;
-                    int rb = __popcll(e0 & lanemask_lt(lane)) +
-                             __popcll(e1 & lanemask_lt(lane));
-                    if (t0) {
-                        int64_t row = j + rb;
-                        if ((row % SEG_ROWS) == 0 &&
-                            row / SEG_ROWS < MAX_SEGS) {
-                            SegEntry E;
-                            E.byte_off =
-                                (uint32_t)(d2_off + pos + 2 * (uint64_t)lane +
-                                           1);
-                            E._pad = 0;
-                            E.v_start = (int64_t)(v_carry +
-                                                  (uint64_t)(int64_t)(pre + dA));
-                            E.d1_start = 0;
-                            bseg[row / SEG_ROWS] = E;
-                        }
-                    }
-                    if (t1) {
-                        int64_t row = j + rb + (t0 ? 1 : 0);
-                        if ((row % SEG_ROWS) == 0 &&
-                            row / SEG_ROWS < MAX_SEGS) {
-                            SegEntry E;
-                            E.byte_off =
-                                (uint32_t)(d2_off + pos + 2 * (uint64_t)lane +
-                                           2);
-                            E._pad = 0;
-                            E.v_start =
-                                (int64_t)(v_carry +
-                                          (uint64_t)(int64_t)(pre + dA + dB));
-                            E.d1_start = 0;
-                            bseg[row / SEG_ROWS] = E;
-                        }
-                    }
-                    v_carry +=
-                        (uint64_t)(int64_t)__builtin_amdgcn_readlane(S, 63);
-                    if (e1 >> 63) {
-                        carry_n2 = 0;
-                        carry_u2 = 0;
-                    } else {
-                        carry_n2 = 1;
-                        carry_u2 = (uint64_t)(
-                            (uint32_t)__builtin_amdgcn_readlane((int)b1, 63) &
-                            0x7f);
-                    }
-                    j += nt;
-                    pos += 128;
-                    continue;
-                }
-            }
-            if (carry_n2) {  // rewind the carried byte for the 64-B walk
-                pos -= carry_n2;
-                carry_n2 = 0;
-                carry_u2 = 0;
-            }
-            uint8_t b = d2s[pos + (uint64_t)lane];
-            uint64_t emask = __ballot(b < 0x80);
-            if (emask == 0) { dev_set_err(derr, DERR_BAD_STREAM, (uint64_t)bi); break; }
-            int rank = __popcll(emask & lanemask_lt(lane));
-            int64_t myj = j + rank;
-            bool is_term = (b < 0x80) && (myj <= n_deltas);
-            uint64_t d = 0;
-            if (emask == ~0ull) {
-                d = (uint64_t)zz_dec(b);
-            } else if (is_term) {
-                uint64_t below = emask & lanemask_lt(lane);
-                int start = below ? (64 - __clzll(below)) : 0;
-                uint64_t u = 0;
-                unsigned sh = 0;
-                for (int i = start; i < lane; ++i) {
-                    u |= (uint64_t)(d2s[pos + (uint64_t)i] & 0x7f) << sh;
-                    sh += 7;
-                }
-                u |= (uint64_t)b << sh;
-                d = (uint64_t)zz_dec(u);
-            }
-            if (!is_term) d = 0;
-            uint64_t s1 = wave_incl_scan(d, lane);
-            uint64_t vinc;
-            uint64_t d1j = 0;
-            if (dod) {
-                // v advances by d1_j = d1_carry + scan(d2); scan the d1_j
-                d1j = is_term ? (d1_carry + s1) : 0;
-                vinc = wave_incl_scan(d1j, lane);
-            } else {
-                vinc = s1;
-            }
-            // a lane whose absolute row is a SEG_ROWS multiple records the
-            // next segment's start (byte after my terminator)
-            int64_t myrow = myj + (dod ? 1 : 0);
-            if (is_term && (myrow % SEG_ROWS) == 0 &&
-                myrow / SEG_ROWS < MAX_SEGS) {
-                SegEntry e;
-                e.byte_off = (uint32_t)(d2_off + pos + (uint64_t)lane + 1);
-                e._pad = 0;
-                e.v_start = (int64_t)(v_carry + vinc);
-                e.d1_start = (int64_t)(d1_carry + s1);
-                bseg[myrow / SEG_ROWS] = e;
-            }
-            int nterm_all = __popcll(emask);
-            int64_t nvals = (n_deltas - j + 1) < (int64_t)nterm_all
-                                ? (n_deltas - j + 1) : (int64_t)nterm_all;
-            int last_lane;
-            if (nvals == (int64_t)nterm_all) {
-                last_lane = 63 - __clzll(emask);
-            } else {
-                uint64_t mm = emask;
-                last_lane = 0;
-                for (int t = 0; t < nvals; t++) {
-                    last_lane = __ffsll((unsigned long long)mm) - 1;
-                    mm &= mm - 1;
-                }
-            }
-            v_carry += (uint64_t)__shfl((long long)vinc, last_lane);
-            if (dod) d1_carry += (uint64_t)__shfl((long long)s1, last_lane);
-            if (j + nterm_all > n_deltas) break;
-            j += nterm_all;
-            pos += (uint64_t)(64 - __clzll(emask));
-        }
-    }
 }
 
 // ---------------- the scan+aggregate kernel ----------------
@@ -2882,7 +2663,7 @@ __device__ void fold_range(const uint8_t *fstream,
 // (~88 atomics/us on one word) and dominates the whole scan; instead block
 // totals fold into these registers and flush only when the group changes
 // or the wave is done.
-// first: the (item << 13 | row) key where this wave first ENTERED the
+// first: the (block << 13 | row) key where this wave first ENTERED the
 // group (rows that pass predicates and map to the group, before the
 // null-field check — matching where the reference's computeKey
 // materialises a group, aggregation.go:523).  The global atomicMin over
@@ -3017,7 +2798,6 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
     const PredBlock *__restrict__ preds_in, int n_preds,
     const uint64_t *__restrict__ pred_bm,
     const uint8_t *__restrict__ pred_flags,
-    const SegEntry *__restrict__ segs_in,
     const GroupBlock *__restrict__ groups_in,
     const uint16_t *__restrict__ gmap_in,
     const uint16_t *__restrict__ gruns_in, int n_gslots, int64_t gm0,
@@ -3031,7 +2811,6 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
         return;
     const int64_t gmul[3] = {gm0, gm1, gm2};
     const PredBlock *preds = EN_PREDS ? preds_in : nullptr;
-    const SegEntry *segs = EN_VALUES ? segs_in : nullptr;
     const GroupBlock *groups = EN_GROUPS ? groups_in : nullptr;
     const int lane = threadIdx.x & 63;
     // In the closed-form instantiations (no value reconstruction, tag
@@ -3054,43 +2833,28 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
 
     WavePartial part;   // flushed on group change / at the end
 
-    // with a segment index, the work item is a (block, segment) pair —
-    // 8x the parallel units on the value-scan path, no serial chain.
+    // The work item is a block: one wave scans a whole block.
     // Strided assignment (not contiguous ranges): predicates skip blocks
     // in long runs, and contiguous ranges turn those runs into idle waves.
-    const int64_t n_items = segs ? n_blocks * MAX_SEGS : n_blocks;
-    // UNI_DESC: the descriptor of the item after this one is requested at
+    // UNI_DESC: the descriptor of the block after this one is requested at
     // the top of each iteration and consumed only when the loop advances,
-    // so its latency hides behind the current block's fold; an item pays
+    // so its latency hides behind the current block's fold; a block pays
     // no descriptor round trip after the wave's first.
     // (Both stay unused, and vanish, in the other instantiations.)
     bydb_block_desc d_cur = {}, d_nxt = {};
-    if (UNI_DESC && wave_id < n_items) d_nxt = blocks[wave_id];
-    for (int64_t wi = wave_id; wi < n_items; wi += n_waves) {
-        const int64_t bi = segs ? wi / MAX_SEGS : wi;
-        const int seg = segs ? (int)(wi % MAX_SEGS) : 0;
+    if (UNI_DESC && wave_id < n_blocks) d_nxt = blocks[wave_id];
+    for (int64_t bi = wave_id; bi < n_blocks; bi += n_waves) {
         if (UNI_DESC) {
             d_cur = d_nxt;   // requested one iteration ago
-            // clamped to the last item, so the request is unconditional
-            int64_t nx = wi + n_waves < n_items ? wi + n_waves : n_items - 1;
+            // clamped to the last block, so the request is unconditional
+            int64_t nx = bi + n_waves < n_blocks ? bi + n_waves : n_blocks - 1;
             d_nxt = blocks[nx];
         }
         // otherwise: issue the independent per-lane loads (descriptor,
-        // predicate flag, segment entries) back-to-back ahead of their
-        // first use
+        // predicate flag) back-to-back ahead of their first use
         const bydb_block_desc *bd = UNI_DESC ? &d_cur : &blocks[bi];
         const uint8_t pf_pre =
             (EN_PREDS && preds != nullptr) ? pred_flags[bi] : PF_CLEAR;
-        uint32_t seg0_off = SEG_INELIGIBLE;
-        SegEntry e_pre;
-        e_pre.byte_off = 0; e_pre._pad = 0; e_pre.v_start = 0;
-        e_pre.d1_start = 0;
-        if (segs) {
-            seg0_off = segs[bi * MAX_SEGS].byte_off;
-            e_pre = segs[bi * MAX_SEGS + seg];
-        }
-        const bool seg_eligible = segs && seg0_off != SEG_INELIGIBLE;
-        if (seg != 0 && !seg_eligible) continue;
         // light/heavy split routing (see the template comment): the heavy
         // pass owns exactly the PF_WALK blocks, the light pass everything
         // else — checked before any clamp work so the off-pass blocks
@@ -3103,7 +2867,6 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
             }
         }
         const int64_t n = (int64_t)bd->count;
-        if (seg != 0 && (int64_t)seg * SEG_ROWS + 1 > n - 1) continue;
         const int64_t ts_min = bd->ts_min, ts_max = bd->ts_max;
         // float64 blocks fold in the decimal-int domain; a block whose
         // exponent EXCEEDS the session's rescales its partials by
@@ -3239,7 +3002,6 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
             }
             // PF_CLEAR: every slot uniform-match -> fold unpredicated
         }
-        bool pred_on = wp0 || wp1 || wp2;
 
         // ---- per-row group-by on dictionary tags (EN_GROUPS) ----
         // Composite keys over up to 3 tag slots: gid = g0 + n0*g1 +
@@ -3278,7 +3040,6 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
                     if (wp1 && wp1->bm) { bw1 = wp1; wp1 = nullptr; }
                     if (wp2 && wp2->bm) { bw2 = wp2; wp2 = nullptr; }
                 }
-                if (seg != 0) continue;  // whole block folded at seg 0
                 const uint8_t *gstream = payload + bd->field_off;
                 const uint8_t *plain_norm =
                     (bd->field_enc == BYDB_ENC_PLAIN &&
@@ -3371,7 +3132,7 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
                             bd->field_first, bd->field_len, n, aa, bb2,
                             EN_VALUES && (flags & KF_NEED_VALUES), raw_f64,
                             lane, bw0, bw1, bw2, derr, (uint64_t)bi, &rf);
-                        part.add(comp, ((uint64_t)wi << 13) | (uint64_t)aa, rf,
+                        part.add(comp, ((uint64_t)bi << 13) | (uint64_t)aa, rf,
                                  flags, fdiff, raw_f64, false, partials,
                                  first_seen, lane, derr, (uint64_t)bi);
                     }
@@ -3384,89 +3145,22 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
                 continue;
             }
         }
-        const bool scan_path =
-            EN_VALUES && (flags & KF_NEED_VALUES) &&
-            ((bd->field_enc == BYDB_ENC_DELTA &&
-              bd->field_len != (uint64_t)(n - 1)) ||
-             bd->field_enc == BYDB_ENC_DELTA_OF_DELTA);
-        const bool use_seg = seg_eligible && scan_path && !pred_on;
-        if (!use_seg && seg != 0) continue;
 
         // ---- field fold ----
         const uint8_t fenc = bd->field_enc;
-        const int64_t first = bd->field_first;
-        const uint8_t *fstream = payload + bd->field_off;
-        RowFold bf;
-        if (use_seg) {
-            const bool dod = fenc == BYDB_ENC_DELTA_OF_DELTA;
-            // (SegEntry preloaded at item start)
-            // segment-parallel value scan: this wave folds only rows
-            // [seg*SEG_ROWS+1 .. min((seg+1)*SEG_ROWS, n-1)] (+ rows 0
-            // and, for delta-of-delta, 1 on segment 0), starting from
-            // the indexed byte offset and carries — no cross-segment
-            // dependency.  For delta-of-delta, segment k >= 1 relabels
-            // absolute row (k*SEG_ROWS - 1 + j'), so j' = 2 lands on
-            // the segment's first row and e.v_start/e.d1_start are the
-            // carries at row k*SEG_ROWS.
-            const SegEntry e = e_pre;
-            int64_t sj_lo = (int64_t)seg * SEG_ROWS + 1;
-            int64_t sj_hi = ((int64_t)seg + 1) * SEG_ROWS;
-            if (sj_hi > n - 1) sj_hi = n - 1;
-            int64_t a = sj_lo > r0 ? sj_lo : r0;
-            int64_t b = sj_hi < r1 ? sj_hi : r1;
-            bool handle0 = seg == 0 && r0 <= 0 && 0 <= r1;
-            bool handle1 = dod && seg == 0 && r0 <= 1 && 1 <= r1;
-            if (dod && seg == 0 && a < 2) a = 2;
-            if (a > b && !handle0 && !handle1) continue;
-            uint64_t lsum = 0, lcnt = 0;
-            int64_t lmn = INT64_MAX, lmx = INT64_MIN;
-            if (a <= b) {
-                ScanFold ff;
-                int64_t rel0 = dod ? ((int64_t)seg * SEG_ROWS -
-                                      (seg ? 1 : 0))
-                                   : (int64_t)seg * SEG_ROWS;
-                scan_stream(fstream + e.byte_off, b - rel0, dod,
-                            e.v_start, e.d1_start, a - rel0, b - rel0,
-                            lane, &ff, derr, (uint64_t)bi, nullptr,
-                            nullptr, nullptr, !EN_CLAMP);
-                lsum = ff.sum;
-                lcnt = ff.nsel;
-                lmn = ff.mn;
-                lmx = ff.mx;
-            }
-            if (lane == 0 && handle0) {
-                lsum += (uint64_t)first;
-                lcnt++;
-                lmn = first < lmn ? first : lmn;
-                lmx = first > lmx ? first : lmx;
-            }
-            if (lane == 0 && handle1) {
-                int64_t row1 = e.v_start;  // seg 0: v at row 1
-                lsum += (uint64_t)row1;
-                lcnt++;
-                lmn = row1 < lmn ? row1 : lmn;
-                lmx = row1 > lmx ? row1 : lmx;
-            }
-            bf.sum = wave_reduce_add(lsum);
-            bf.cnt = wave_reduce_add(lcnt);
-            bf.mn = wave_reduce_min(lmn);
-            bf.mx = wave_reduce_max(lmx);
-            bf.have_mm = bf.cnt > 0;
-        } else {
-            const uint8_t *plain_norm =
-                (fenc == BYDB_ENC_PLAIN && (bd->field_off & TAG_SIDECAR_BIT))
-                    ? sidecar + (bd->field_off & ~TAG_SIDECAR_BIT)
-                    : nullptr;
-            bf = fold_rows<EN_VALUES, !EN_CLAMP,
-                           !UNI_DESC ? DENSE_CALL
-                                     : EN_STREAM ? DENSE_INLINE_NT
-                                                 : DENSE_INLINE>(
-                fstream, plain_norm, fenc, first, bd->field_len, n, r0, r1,
-                (flags & KF_NEED_VALUES) != 0, raw_f64, lane, wp0, wp1, wp2,
-                derr, (uint64_t)bi);
-        }
+        const uint8_t *plain_norm =
+            (fenc == BYDB_ENC_PLAIN && (bd->field_off & TAG_SIDECAR_BIT))
+                ? sidecar + (bd->field_off & ~TAG_SIDECAR_BIT)
+                : nullptr;
+        const RowFold bf =
+            fold_rows<EN_VALUES, !EN_CLAMP,
+                      !UNI_DESC ? DENSE_CALL
+                                : EN_STREAM ? DENSE_INLINE_NT : DENSE_INLINE>(
+                payload + bd->field_off, plain_norm, fenc, bd->field_first,
+                bd->field_len, n, r0, r1, (flags & KF_NEED_VALUES) != 0,
+                raw_f64, lane, wp0, wp1, wp2, derr, (uint64_t)bi);
         // a rescale overflow drops the block
-        part.add(block_group, ((uint64_t)wi << 13) | (uint64_t)r0, bf, flags,
+        part.add(block_group, ((uint64_t)bi << 13) | (uint64_t)r0, bf, flags,
                  fdiff, raw_f64, true, partials, first_seen, lane, derr,
                  (uint64_t)bi);
     }
@@ -3942,9 +3636,6 @@ struct bydb_session {
     DevErr *d_err = nullptr;
     PredBlock *d_preds = nullptr;
     int64_t preds_cap = 0;
-    SegEntry *d_segs = nullptr;
-    int64_t segs_cap = 0;
-    bool segs_built = false;
     // per-row group-by on dictionary tags (composite keys over <=3 slots)
     int n_gslots = 0;                  // 0 = group by block group_code
     int gslots[3] = {-1, -1, -1};
@@ -4090,7 +3781,6 @@ extern "C" void bydb_session_destroy(bydb_session *s) {
     if (s->d_partials) (void)hipFree(s->d_partials);
     if (s->d_preds) (void)hipFree(s->d_preds);
     if (s->d_filter) (void)hipFree(s->d_filter);
-    if (s->d_segs) (void)hipFree(s->d_segs);
     if (s->d_groups) (void)hipFree(s->d_groups);
     if (s->d_gmap) (void)hipFree(s->d_gmap);
     if (s->d_gruns) (void)hipFree(s->d_gruns);
@@ -4139,7 +3829,6 @@ extern "C" int bydb_part_reserve(bydb_session *s, uint64_t payload_bytes,
     s->part_ts_max = INT64_MIN;
     s->sidecar_len = 0;
     s->n_plain_host = 0;
-    s->segs_built = false;
     s->groups_built = false;
     s->dedup_built = false;
     return BYDB_OK;
@@ -4149,7 +3838,6 @@ extern "C" int bydb_part_append(bydb_session *s, const uint8_t *payload,
                                 uint64_t len, const bydb_block_desc *blocks,
                                 int64_t n_blocks) {
     HIP_TRY(s, hipSetDevice(s->device));
-    s->segs_built = false;
     s->groups_built = false;
     s->dedup_built = false;
     if (s->payload_len + len > s->payload_cap ||
@@ -4438,8 +4126,8 @@ static int ensure_pred_buffers(bydb_session *s) {
     return BYDB_OK;
 }
 
-// The scan launch shared by every consume entry point: segment index and
-// group resolve (once per part), kernel selection, light + heavy pass.
+// The scan launch shared by every consume entry point: group resolve (once
+// per part), kernel selection, light + heavy pass.
 static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
                        PredBlock *preds, int n_preds) {
     int flags = 0;
@@ -4448,27 +4136,6 @@ static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
     if (s->field_vtype == BYDB_VT_FLOAT64)
         flags |= KF_FLOAT | ((int)(uint16_t)s->float_exp << 16);
     const int threads = 256;                       // 4 waves per workgroup
-    SegEntry *segs = nullptr;
-    if (flags & KF_NEED_VALUES) {
-        // build (once per part) and use the varint segment index
-        if (s->segs_cap < s->n_blocks * MAX_SEGS) {
-            if (s->d_segs) (void)hipFree(s->d_segs);
-            HIP_TRY(s, hipMalloc(&s->d_segs, sizeof(SegEntry) *
-                                                 (size_t)s->n_blocks * MAX_SEGS));
-            s->segs_cap = s->n_blocks * MAX_SEGS;
-            s->segs_built = false;
-        }
-        if (!s->segs_built) {
-            int64_t wgs_b = (s->n_blocks + 3) / 4;
-            int grid_b = (int)(wgs_b < 8192 ? wgs_b : 8192);
-            hipLaunchKernelGGL(k_build_seg_index, dim3(grid_b), dim3(threads),
-                               0, s->stream, s->d_payload, s->d_blocks,
-                               s->n_blocks, s->d_segs, s->d_err);
-            HIP_TRY(s, hipGetLastError());
-            s->segs_built = true;
-        }
-        segs = s->d_segs;
-    }
     GroupBlock *groups = nullptr;
     if (s->n_gslots > 0) {
         if (s->groups_cap < s->n_blocks) {
@@ -4536,8 +4203,7 @@ static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
         }
         groups = s->d_groups;
     }
-    int64_t waves_needed = segs ? s->n_blocks * MAX_SEGS : s->n_blocks;
-    int64_t wgs = (waves_needed + 3) / 4;
+    int64_t wgs = (s->n_blocks + 3) / 4;            // one wave per block
     int grid = (int)(wgs < 8192 ? wgs : 8192);     // grid-stride beyond
     if (grid < 1) grid = 1;
     HIP_TRY(s, hipEventRecord(s->ev_start, s->stream));
@@ -4591,7 +4257,7 @@ static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
         hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), 0, s->stream,
                            s->d_payload, s->d_sidecar, s->d_blocks,
                            s->n_blocks, min_ts, max_ts, pass_flags, preds,
-                           n_preds, s->d_pred_bm, s->d_pred_flags, segs,
+                           n_preds, s->d_pred_bm, s->d_pred_flags,
                            groups, s->d_gmap, s->d_gruns, s->n_gslots,
                            s->gmul[0], s->gmul[1], s->gmul[2],
                            (int64_t)s->n_groups, s->d_acc, s->d_err,
