@@ -17,6 +17,7 @@ VT_FLOAT64 = 3
 AGG_SUM, AGG_COUNT, AGG_MIN, AGG_MAX, AGG_MEAN = range(5)
 MODE_ALL, MODE_MAP, MODE_REDUCE = range(3)
 STREAM_AUTO, STREAM_CACHED, STREAM_STREAMING = range(3)
+PACK_AUTO, PACK_OFF, PACK_ON = range(3)
 INT64_MIN = -(2 ** 63)
 FLOAT_RAW_EXP = -32768  # sessions over nullable float64 columns
 INT64_MAX = 2 ** 63 - 1
@@ -222,6 +223,22 @@ def filter_nodes_table(nodes, n_conds):
     return sum(int(out[w]) << (64 * w) for w in range(4))
 
 
+def field_pack_plan(descs):
+    """The slot planner of the nibble-packed dense field streams over a list
+    of BlockDesc: ([slot_off], [slot_len], arena_bytes); slot_len 0 marks a
+    block that is no candidate.  Pure host."""
+    n = len(descs)
+    arr = (BlockDesc * max(n, 1))(*descs)
+    offs = (C.c_uint64 * max(n, 1))()
+    lens = (C.c_uint32 * max(n, 1))()
+    arena = C.c_uint64(0)
+    rc = _lib.bydb_field_pack_plan(arr, n, offs, lens, C.byref(arena))
+    if rc != 0:
+        raise ValueError(f"bydb_field_pack_plan rc={rc}")
+    return ([int(offs[i]) for i in range(n)],
+            [int(lens[i]) for i in range(n)], int(arena.value))
+
+
 def row_dedup_peers(descs):
     """The overlap planner of the cross-part version dedup over a list of
     BlockDesc (only series_id, ts_min and ts_max are read): per block the
@@ -337,6 +354,15 @@ def _load():
     lib.bydb_set_stream_policy.argtypes = [C.c_void_p, C.c_int]
     lib.bydb_stream_policy_pick.restype = C.c_int
     lib.bydb_stream_policy_pick.argtypes = [C.c_int, C.c_uint64]
+    lib.bydb_set_field_pack.restype = C.c_int
+    lib.bydb_set_field_pack.argtypes = [C.c_void_p, C.c_int]
+    lib.bydb_field_pack_stats.restype = C.c_int
+    lib.bydb_field_pack_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.bydb_field_pack_plan.restype = C.c_int
+    lib.bydb_field_pack_plan.argtypes = [bp, C.c_int64,
+                                         C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_uint64)]
     lib.bydb_last_consume_ms.restype = C.c_double
     lib.bydb_last_consume_ms.argtypes = [C.c_void_p]
     lib.bydb_group_first_seen.restype = C.c_int
@@ -727,6 +753,19 @@ class Session:
         """STREAM_AUTO (default), STREAM_CACHED or STREAM_STREAMING: how
         the closed-form scan loads the dense delta streams."""
         self._ck(_lib.bydb_set_stream_policy(self._h, policy))
+
+    def set_field_pack(self, mode):
+        """PACK_AUTO (default), PACK_OFF or PACK_ON: whether the closed-form
+        streaming scan reads a 4-bit copy of the dense delta streams whose
+        deltas all lie in [-8, 7]."""
+        self._ck(_lib.bydb_set_field_pack(self._h, mode))
+
+    def field_pack_stats(self):
+        """[candidate blocks, packed blocks, packed payload bytes, slot
+        arena bytes] of the resident part; zeros before the build."""
+        out = (C.c_uint64 * 4)()
+        self._ck(_lib.bydb_field_pack_stats(self._h, out))
+        return [int(x) for x in out]
 
     def last_consume_ms(self):
         return _lib.bydb_last_consume_ms(self._h)

@@ -455,6 +455,102 @@ __device__ void dense_region(const uint8_t *stream, int64_t lo, int64_t hi,
                                              out_sum_jd);
 }
 
+// ---- nibble-packed dense delta fold ----
+// A dense block whose deltas all lie in [-8, 7] has a 4-bit copy in the
+// packed arena (pack_build): nibble p of the slot (byte p/2, low nibble
+// first) holds delta p+1 biased by 8, and every nibble from the block's
+// last delta to the slot's end holds 8, that is delta 0.  A slot is a
+// multiple of 128 bytes on a 128-byte boundary, so the fold reads whole
+// 16-byte lane units and masks nothing.
+#define PACK_SLOT_ALIGN 128
+#define PACK_CHUNKS_BLOCK 4     // 8191 nibbles are exactly four 1-KiB chunks
+#define PACK_MAX_ROWS 8192
+#define PACK_PAD_WORD 0x88888888u
+
+__host__ __device__ __forceinline__ uint32_t pack_slot_bytes(uint32_t count) {
+    return (count / 2 + (PACK_SLOT_ALIGN - 1)) & ~(uint32_t)(PACK_SLOT_ALIGN - 1);
+}
+
+// Fold one lane's 16 bytes = 32 nibbles: T = sum of the 32 deltas, K = sum
+// of (nibble position within the 32) * delta.  Two masks split a dword into
+// its even and odd nibbles as byte lanes; the biased nibbles (0..15) and the
+// position weights (0..31) are non-negative i8, so the signed dot4 folds
+// them as they are, and the bias leaves through the accumulators' start
+// values: 32 * 8 for T, 8 * (0 + 1 + ... + 31) for K.  The eight nibble
+// lanes of one byte position sum to <= 120, so T takes a single dot4.
+__device__ __forceinline__ void packed_fold16(u32x4 w, int32_t *T, int32_t *K) {
+    const uint32_t m = 0x0f0f0f0fu;
+    uint32_t e0 = w.x & m, o0 = (w.x >> 4) & m, e1 = w.y & m, o1 = (w.y >> 4) & m,
+             e2 = w.z & m, o2 = (w.z >> 4) & m, e3 = w.w & m, o3 = (w.w >> 4) & m;
+    *T = dot4_i8(((e0 + o0) + (e1 + o1)) + ((e2 + o2) + (e3 + o3)),
+                 0x01010101u, -32 * 8);
+    *K = dot4_i8(e0, 0x06040200u, dot4_i8(o0, 0x07050301u,
+         dot4_i8(e1, 0x0e0c0a08u, dot4_i8(o1, 0x0f0d0b09u,
+         dot4_i8(e2, 0x16141210u, dot4_i8(o2, 0x17151311u,
+         dot4_i8(e3, 0x1e1c1a18u, dot4_i8(o3, 0x1f1d1b19u, -8 * 496))))))));
+}
+
+// Sum(d_j) and Sum(p * d_j) over a whole block's slot (delta j at nibble
+// p = j - 1), per lane: the caller reduces.  n_rows must be wave-uniform.
+// The loads are non-temporal (only the streaming instantiations come here)
+// and, as in dense_region_t, all of a block's chunks are issued before the
+// first is folded; a full-length block folds under counted waits.  Only the
+// lanes whose 16 bytes lie inside the slot load, so nothing is read past it.
+// int32 per lane: 128 nibbles * |d| <= 8 * position <= 8191 is about 8.4e6.
+__device__ __forceinline__ void dense_region_packed(
+    const uint8_t *slot, uint32_t n_rows, int lane, int64_t *out_sum_d,
+    int64_t *out_sum_pd) {
+    const int32_t slot_bytes = (int32_t)pack_slot_bytes(n_rows);
+    const gptr_u4 p = (gptr_u4)slot + lane;
+    const int32_t lane_off = lane * 16;
+    int32_t acc_d = 0, acc_c = 0, acc_k = 0;
+    auto fold = [&](int c, u32x4 v) {
+        int32_t T, K;
+        packed_fold16(v, &T, &K);
+        acc_d += T;
+        acc_c += __mul24(c, T);
+        acc_k += K;
+    };
+    u32x4 w[PACK_CHUNKS_BLOCK];
+    if (slot_bytes == PACK_CHUNKS_BLOCK * DENSE_CHUNK_BYTES) {
+#pragma unroll
+        for (int c = 0; c < PACK_CHUNKS_BLOCK; c++)
+            w[c] = __builtin_nontemporal_load(p + c * 64);
+#pragma unroll
+        for (int c = 0; c < PACK_CHUNKS_BLOCK; c++) {
+            fold(c, w[c]);
+            // keep the folds in issue order (see dense_region_t)
+            asm volatile("" : "+v"(acc_d), "+v"(acc_c), "+v"(acc_k));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < PACK_CHUNKS_BLOCK; c++) {
+            w[c] = u32x4{PACK_PAD_WORD, PACK_PAD_WORD, PACK_PAD_WORD,
+                         PACK_PAD_WORD};
+            if (c * DENSE_CHUNK_BYTES + lane_off < slot_bytes)
+                w[c] = __builtin_nontemporal_load(p + c * 64);
+        }
+#pragma unroll
+        for (int c = 0; c < PACK_CHUNKS_BLOCK; c++)
+            if (c * DENSE_CHUNK_BYTES < slot_bytes) fold(c, w[c]);
+    }
+    *out_sum_d = (int64_t)acc_d;
+    *out_sum_pd = (int64_t)(2 * lane_off * acc_d +
+                            2 * DENSE_CHUNK_BYTES * acc_c + acc_k);
+}
+
+// The whole-block weighted fold over a slot: delta j = p + 1 of an n-row
+// block weighs n - j = n - 1 - p (dense_delta_weighted_t with r0 = 0,
+// r1 = n - 1).
+__device__ __forceinline__ uint64_t dense_packed_weighted(const uint8_t *slot,
+                                                          uint32_t n_rows,
+                                                          int lane) {
+    int64_t sd, spd;
+    dense_region_packed(slot, n_rows, lane, &sd, &spd);
+    return (uint64_t)(n_rows - 1) * (uint64_t)sd - (uint64_t)spd;
+}
+
 // wave-wide inclusive scan of an int32 (per-window lane sums)
 // row-masked DPP: rows outside ROWMASK receive `old` = 0, so `v += ...`
 // is a no-op there — the canonical GCN cross-row scan combine.
@@ -2434,7 +2530,8 @@ __device__ __forceinline__ RowFold fold_rows(
     const uint8_t *fstream, const uint8_t *plain_norm, uint8_t fenc,
     int64_t first, uint64_t field_len, int64_t n, int64_t a, int64_t b,
     bool need_values, bool raw_f64, int lane, PredWalk *w0, PredWalk *w1,
-    PredWalk *w2, DevErr *derr, uint64_t bi) {
+    PredWalk *w2, DevErr *derr, uint64_t bi,
+    const uint8_t *packed = nullptr) {
     need_values = EN_VALUES && need_values;
     const uint64_t nsel = (uint64_t)(b - a + 1);
     const bool pred_on = w0 || w1 || w2;
@@ -2566,6 +2663,10 @@ __device__ __forceinline__ RowFold fold_rows(
                                            bi);
         } else if (DENSE == DENSE_CALL || need_values) {
             acc = dense_delta_weighted(fstream, n - 1, a, b, lane);
+        } else if (DENSE == DENSE_INLINE_NT && packed != nullptr && a == 0 &&
+                   b == n - 1) {
+            // whole block with a 4-bit copy: half the bytes
+            acc = dense_packed_weighted(packed, (uint32_t)n, lane);
         } else {
             // dense dot4 fold, the whole block in flight
             acc = dense_delta_weighted_t<FULL ? DENSE_CHUNKS_BLOCK
@@ -2769,7 +2870,9 @@ struct WavePartial {
 // spill scratch reloads into the dense fold loop (~7% on the headline).
 // EN_STREAM — the closed-form instantiations only: the dense fold reads
 // its chunks with non-temporal loads (dense_region_t).  The host picks it
-// per pass from the session's stream-load policy.
+// per pass from the session's stream-load policy.  These instantiations
+// also read the nibble-packed copy of a block where `pack` has one, for a
+// block folded whole; a block cut by the clamp folds from its byte stream.
 template <bool EN_VALUES, bool EN_PREDS, bool EN_GROUPS, bool EN_WALK,
           bool EN_CLAMP, bool EN_STREAM = false>
 // Occupancy: 4 waves/SIMD for the value-scan instantiations — requesting
@@ -2804,7 +2907,7 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
     int64_t gm1, int64_t gm2, int64_t n_groups,
     bydb_partial *__restrict__ partials, DevErr *derr,
     const uint32_t *__restrict__ walk_count,
-    uint64_t *__restrict__ first_seen) {
+    uint64_t *__restrict__ first_seen, const uint8_t *__restrict__ pack) {
     // heavy pass with no PF_WALK blocks anywhere: one scalar load, done
     if ((flags & KF_WALK_ONLY) && walk_count != nullptr &&
         *walk_count == 0)
@@ -2818,7 +2921,11 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
     // the wave index goes through readfirstlane, so the item index and the
     // descriptor live in scalar registers and the descriptor is fetched by
     // scalar loads (descriptors are written by host copies before the
-    // launch, so the read-only scalar cache is safe for them).
+    // launch, so the read-only scalar cache is safe for them).  The
+    // packed-slot table at the head of `pack` goes the same way although a
+    // kernel wrote it (k_pack_fields): that kernel ran in an EARLIER launch
+    // on this stream, and the scalar cache holds nothing across a launch
+    // boundary, so no entry can be read stale.
     // Not with EN_GROUPS: the run-merge state leaves no scalar registers
     // for two descriptors, and what spills there lands in scratch.  Not
     // with EN_PREDS: a skipped block costs one flag byte there, and
@@ -2842,13 +2949,26 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
     // no descriptor round trip after the wave's first.
     // (Both stay unused, and vanish, in the other instantiations.)
     bydb_block_desc d_cur = {}, d_nxt = {};
-    if (UNI_DESC && wave_id < n_blocks) d_nxt = blocks[wave_id];
+    // PACKED: the block's entry of the packed-slot table (0: no 4-bit copy,
+    // else the slot's offset from `pack` in 128-byte units) travels with
+    // the descriptor, one block ahead.  pack is null when nothing is packed.
+    constexpr bool PACKED = UNI_DESC && EN_STREAM;
+    const uint32_t *pack_off = (const uint32_t *)pack;
+    uint32_t po_cur = 0, po_nxt = 0;
+    if (UNI_DESC && wave_id < n_blocks) {
+        d_nxt = blocks[wave_id];
+        if (PACKED && pack != nullptr) po_nxt = pack_off[wave_id];
+    }
     for (int64_t bi = wave_id; bi < n_blocks; bi += n_waves) {
         if (UNI_DESC) {
             d_cur = d_nxt;   // requested one iteration ago
             // clamped to the last block, so the request is unconditional
             int64_t nx = bi + n_waves < n_blocks ? bi + n_waves : n_blocks - 1;
             d_nxt = blocks[nx];
+            if (PACKED && pack != nullptr) {
+                po_cur = po_nxt;
+                po_nxt = pack_off[nx];
+            }
         }
         // otherwise: issue the independent per-lane loads (descriptor,
         // predicate flag) back-to-back ahead of their first use
@@ -3158,7 +3278,10 @@ __global__ __launch_bounds__(256, (EN_VALUES && !EN_CLAMP && !EN_GROUPS) ? 8 : (
                                 : EN_STREAM ? DENSE_INLINE_NT : DENSE_INLINE>(
                 payload + bd->field_off, plain_norm, fenc, bd->field_first,
                 bd->field_len, n, r0, r1, (flags & KF_NEED_VALUES) != 0,
-                raw_f64, lane, wp0, wp1, wp2, derr, (uint64_t)bi);
+                raw_f64, lane, wp0, wp1, wp2, derr, (uint64_t)bi,
+                (PACKED && po_cur != 0)
+                    ? pack + (uint64_t)po_cur * PACK_SLOT_ALIGN
+                    : nullptr);
         // a rescale overflow drops the block
         part.add(block_group, ((uint64_t)bi << 13) | (uint64_t)r0, bf, flags,
                  fdiff, raw_f64, true, partials, first_seen, lane, derr,
@@ -3612,6 +3735,70 @@ __global__ void k_reset_partials(bydb_partial *p, int64_t n) {
     }
 }
 
+// ---------------- nibble-packed dense field streams ----------------
+// A dense one-byte delta stream whose zigzag bytes are all <= 15 carries
+// four bits of information per byte.  Parts are immutable and stay
+// resident, so such streams get a 4-bit copy, built once per part
+// (pack_build) and read by the streaming closed-form scan in place of the
+// byte stream (dense_region_packed).  The planner decides from the
+// descriptors alone which blocks get a slot; whether a slot is filled is
+// decided here, from the bytes.
+
+// A block is a candidate when its field stream is a dense one-byte delta
+// stream in the payload arena.
+__host__ __device__ __forceinline__ bool pack_candidate(
+    const bydb_block_desc *bd) {
+    return bd->field_enc == BYDB_ENC_DELTA && bd->count >= 2 &&
+           bd->count <= PACK_MAX_ROWS &&
+           bd->field_len == (uint64_t)bd->count - 1 &&
+           !(bd->field_off & TAG_SIDECAR_BIT);
+}
+
+#define PACK_CTR_BLOCKS 0
+#define PACK_CTR_BYTES 1
+
+// One wave per planned block.  table[bi] arrives as the planner's slot
+// (offset from `pack` in 128-byte units, 0: no slot) and leaves as 0 where
+// a byte of the stream exceeds 15: that block stays with its byte stream,
+// its slot is wasted.  The pad nibbles up to the slot's end are 8 (delta 0).
+__global__ __launch_bounds__(WAVE) void k_pack_fields(
+    const uint8_t *__restrict__ payload,
+    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
+    uint8_t *__restrict__ pack, unsigned long long *__restrict__ ctr) {
+    const int lane = threadIdx.x;
+    uint32_t *table = (uint32_t *)pack;
+    for (int64_t bi = blockIdx.x; bi < n_blocks; bi += gridDim.x) {
+        const uint32_t unit = table[bi];
+        if (unit == 0) continue;
+        const bydb_block_desc *bd = &blocks[bi];
+        const uint8_t *stream = payload + bd->field_off;
+        const uint32_t len = bd->count - 1;
+        uint32_t seen = 0;
+        for (uint32_t i = lane; i < len; i += WAVE) seen |= stream[i];
+        if (__any(seen > 15u)) {
+            if (lane == 0) table[bi] = 0;
+            continue;
+        }
+        uint8_t *slot = pack + (uint64_t)unit * PACK_SLOT_ALIGN;
+        const uint32_t slot_bytes = pack_slot_bytes(bd->count);
+        for (uint32_t q = lane; q < slot_bytes; q += WAVE) {
+            // zigzag byte z <= 15 -> delta (z >> 1) ^ -(z & 1), biased by 8
+            uint32_t nib[2];
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const uint32_t i = 2 * q + k;
+                const uint32_t z = i < len ? stream[i] : 0;
+                nib[k] = (uint32_t)((int32_t)((z >> 1) ^ (0u - (z & 1u))) + 8);
+            }
+            slot[q] = (uint8_t)(nib[0] | (nib[1] << 4));
+        }
+        if (lane == 0) {
+            atomicAdd(&ctr[PACK_CTR_BLOCKS], 1ull);
+            atomicAdd(&ctr[PACK_CTR_BYTES], (unsigned long long)((len + 1) / 2));
+        }
+    }
+}
+
 // ===================== host session =====================
 
 struct bydb_session {
@@ -3695,6 +3882,15 @@ struct bydb_session {
     uint32_t *d_dd_plist = nullptr, *d_dd_flist = nullptr;
     unsigned long long *d_dd_ctr = nullptr;
     uint64_t dd_bm_base = 0;   // first pred_bm word of the merged bitmaps
+    // nibble-packed dense field streams (bydb_set_field_pack): derived
+    // state over the resident part, built on the first consume that reads
+    // it.  d_pack: the slot table (n_blocks x u32) followed by the slots;
+    // null when the build packed nothing.
+    int field_pack = BYDB_PACK_AUTO;
+    bool pack_built = false;
+    uint8_t *d_pack = nullptr;
+    unsigned long long *d_pack_ctr = nullptr;
+    uint64_t pack_stats[4] = {0, 0, 0, 0};
 };
 
 // What a read-once pass has to exceed before its loads bypass the caches:
@@ -3743,6 +3939,12 @@ static void dedup_free(bydb_session *s) {
     s->d_dd_peers = nullptr; s->d_dd_arena = nullptr;
     s->d_dd_surv = nullptr; s->d_dd_plist = nullptr;
     s->d_dd_flist = nullptr; s->d_dd_ctr = nullptr;
+}
+
+static void pack_free(bydb_session *s) {
+    if (s->d_pack) (void)hipFree(s->d_pack);
+    s->d_pack = nullptr;
+    for (int i = 0; i < 4; i++) s->pack_stats[i] = 0;
 }
 
 extern "C" bydb_session *bydb_session_create(int device) {
@@ -3800,6 +4002,8 @@ extern "C" void bydb_session_destroy(bydb_session *s) {
     if (s->d_tree_stats) (void)hipFree(s->d_tree_stats);
     if (s->d_first_seen) (void)hipFree(s->d_first_seen);
     dedup_free(s);
+    pack_free(s);
+    if (s->d_pack_ctr) (void)hipFree(s->d_pack_ctr);
     if (s->ev_start) (void)hipEventDestroy(s->ev_start);
     if (s->ev_stop) (void)hipEventDestroy(s->ev_stop);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -3815,6 +4019,9 @@ extern "C" int bydb_part_reserve(bydb_session *s, uint64_t payload_bytes,
     HIP_TRY(s, hipSetDevice(s->device));
     if (s->d_payload) { (void)hipFree(s->d_payload); s->d_payload = nullptr; }
     if (s->d_blocks) { (void)hipFree(s->d_blocks); s->d_blocks = nullptr; }
+    // the packed copy of the old part goes before the new payload is
+    // allocated: it is up to half the old payload again
+    pack_free(s);
     // +4KiB slack: the 256-byte quad-window loop runs an 8-window-deep
     // load pipeline (2 KiB of lead) and may read past the last stream's
     // end
@@ -3831,6 +4038,7 @@ extern "C" int bydb_part_reserve(bydb_session *s, uint64_t payload_bytes,
     s->n_plain_host = 0;
     s->groups_built = false;
     s->dedup_built = false;
+    s->pack_built = false;
     return BYDB_OK;
 }
 
@@ -3840,6 +4048,7 @@ extern "C" int bydb_part_append(bydb_session *s, const uint8_t *payload,
     HIP_TRY(s, hipSetDevice(s->device));
     s->groups_built = false;
     s->dedup_built = false;
+    s->pack_built = false;
     if (s->payload_len + len > s->payload_cap ||
         s->n_blocks + n_blocks > s->blocks_cap) {
         s->err = "part_append exceeds reservation";
@@ -3957,6 +4166,9 @@ extern "C" int bydb_part_append(bydb_session *s, const uint8_t *payload,
     return BYDB_OK;
 }
 
+// The derived state (groups, dedup survivors, packed copy) is not
+// invalidated here: with n_blocks == 0 no scan reads any of it, and the
+// append that makes the part non-empty again invalidates all three.
 extern "C" int bydb_part_clear(bydb_session *s) {
     s->payload_len = 0;
     s->n_blocks = 0;
@@ -4126,6 +4338,150 @@ static int ensure_pred_buffers(bydb_session *s) {
     return BYDB_OK;
 }
 
+// ---- nibble-packed dense field streams: planner, build ----
+// (kernel: k_pack_fields; fold: dense_region_packed)
+
+// The slot planner.  Every candidate gets ceil((count-1)/2) bytes rounded
+// up to a 128-byte multiple, slots laid end to end from offset 0 in block
+// order: 128-byte aligned, pairwise disjoint, no memory line shared.
+static uint64_t plan_pack(const bydb_block_desc *blocks, int64_t n,
+                          uint64_t *slot_off, uint32_t *slot_len,
+                          uint64_t *n_cand) {
+    uint64_t at = 0, cand = 0;
+    for (int64_t i = 0; i < n; i++) {
+        const bool c = pack_candidate(&blocks[i]);
+        const uint32_t len = c ? pack_slot_bytes(blocks[i].count) : 0;
+        if (slot_off) slot_off[i] = c ? at : 0;
+        if (slot_len) slot_len[i] = len;
+        at += len;
+        cand += c;
+    }
+    if (n_cand) *n_cand = cand;
+    return at;
+}
+
+extern "C" int bydb_field_pack_plan(const bydb_block_desc *blocks,
+                                    int64_t n_blocks, uint64_t *slot_off,
+                                    uint32_t *slot_len,
+                                    uint64_t *arena_bytes) {
+    if (n_blocks < 0 || (n_blocks > 0 && blocks == nullptr) ||
+        (n_blocks > 0 && (slot_off == nullptr || slot_len == nullptr)) ||
+        arena_bytes == nullptr)
+        return BYDB_ERR_BAD_ARG;
+    *arena_bytes = plan_pack(blocks, n_blocks, slot_off, slot_len, nullptr);
+    return BYDB_OK;
+}
+
+extern "C" int bydb_set_field_pack(bydb_session *s, int mode) {
+    if (mode != BYDB_PACK_AUTO && mode != BYDB_PACK_OFF &&
+        mode != BYDB_PACK_ON) {
+        s->err = "unknown field pack mode";
+        return BYDB_ERR_BAD_ARG;
+    }
+    // a change of mode drops the copy: what the new mode does not read must
+    // not stay resident, and what it reads is built again by its first
+    // consume (also after a build that fell back to the byte streams)
+    if (mode != s->field_pack) {
+        HIP_TRY(s, hipSetDevice(s->device));
+        pack_free(s);
+        s->pack_built = false;
+    }
+    s->field_pack = mode;
+    return BYDB_OK;
+}
+
+// The closed-form scan would read packed data under the session's current
+// mode and stream-load policy.
+static bool pack_wanted(const bydb_session *s) {
+    return s->field_pack == BYDB_PACK_ON ||
+           (s->field_pack == BYDB_PACK_AUTO &&
+            bydb_stream_policy_pick(s->stream_policy, s->payload_len) ==
+                BYDB_STREAM_STREAMING);
+}
+
+extern "C" int bydb_field_pack_stats(bydb_session *s, uint64_t out[4]) {
+    const bool live = s->pack_built && pack_wanted(s);
+    for (int i = 0; i < 4; i++) out[i] = live ? s->pack_stats[i] : 0;
+    return BYDB_OK;
+}
+
+// Once per resident part, on the first closed-form streaming consume with
+// packing on: read the descriptors back, plan the slots, pack on the
+// device, and read the two counters back — the build's single host wait.
+// A part without candidates allocates nothing.  An allocation failure
+// leaves the part unpacked: silently under AUTO, as BYDB_ERR_OOM under ON.
+static int pack_build(bydb_session *s) {
+    if (s->pack_built) return BYDB_OK;
+    pack_free(s);
+    const int64_t nb = s->n_blocks;
+    // slot offsets are table entries in 128-byte units
+    if (nb < 1 || nb > (int64_t)UINT32_MAX) {
+        s->pack_built = true;
+        return BYDB_OK;
+    }
+    std::vector<bydb_block_desc> hb((size_t)nb);
+    HIP_TRY(s, hipMemcpy(hb.data(), s->d_blocks,
+                         sizeof(bydb_block_desc) * (size_t)nb,
+                         hipMemcpyDeviceToHost));
+    std::vector<uint64_t> off((size_t)nb);
+    std::vector<uint32_t> len((size_t)nb);
+    uint64_t n_cand = 0;
+    const uint64_t arena = plan_pack(hb.data(), nb, off.data(), len.data(),
+                                     &n_cand);
+    s->pack_stats[0] = n_cand;
+    const uint64_t table_bytes =
+        ((uint64_t)nb * sizeof(uint32_t) + PACK_SLOT_ALIGN - 1) &
+        ~(uint64_t)(PACK_SLOT_ALIGN - 1);
+    const uint64_t bytes = table_bytes + arena;
+    if (n_cand == 0 || bytes / PACK_SLOT_ALIGN > (uint64_t)UINT32_MAX) {
+        s->pack_built = true;
+        return BYDB_OK;
+    }
+    if (hipMalloc(&s->d_pack, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        s->d_pack = nullptr;
+        s->pack_built = true;   // unpacked until the part or the mode changes
+        if (s->field_pack != BYDB_PACK_ON) return BYDB_OK;
+        char buf[160];
+        snprintf(buf, sizeof buf,
+                 "field pack: cannot allocate %llu bytes for the packed "
+                 "arena; the part stays unpacked",
+                 (unsigned long long)bytes);
+        s->err = buf;
+        return BYDB_ERR_OOM;
+    }
+    if (!s->d_pack_ctr)
+        HIP_TRY(s, hipMalloc(&s->d_pack_ctr, 2 * sizeof(unsigned long long)));
+    std::vector<uint32_t> table((size_t)(table_bytes / sizeof(uint32_t)), 0);
+    for (int64_t i = 0; i < nb; i++)
+        if (len[(size_t)i])
+            table[(size_t)i] =
+                (uint32_t)((table_bytes + off[(size_t)i]) / PACK_SLOT_ALIGN);
+    HIP_TRY(s, hipMemcpyAsync(s->d_pack, table.data(), table_bytes,
+                              hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(s, hipMemsetAsync(s->d_pack_ctr, 0, 2 * sizeof(unsigned long long),
+                              s->stream));
+    const int grid = (int)(nb < 65535 ? nb : 65535);
+    hipLaunchKernelGGL(k_pack_fields, dim3(grid), dim3(WAVE), 0, s->stream,
+                       s->d_payload, s->d_blocks, nb, s->d_pack, s->d_pack_ctr);
+    HIP_TRY(s, hipGetLastError());
+    unsigned long long h_ctr[2] = {0, 0};
+    HIP_TRY(s, hipMemcpyAsync(h_ctr, s->d_pack_ctr, sizeof h_ctr,
+                              hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    s->pack_stats[1] = h_ctr[PACK_CTR_BLOCKS];
+    s->pack_stats[2] = h_ctr[PACK_CTR_BYTES];
+    s->pack_stats[3] = arena;
+    if (h_ctr[PACK_CTR_BLOCKS] == 0) {
+        // nothing qualified: the scan gets no table
+        (void)hipFree(s->d_pack);
+        s->d_pack = nullptr;
+        s->pack_stats[3] = 0;
+    }
+    s->pack_built = true;
+    return BYDB_OK;
+}
+
 // The scan launch shared by every consume entry point: group resolve (once
 // per part), kernel selection, light + heavy pass.
 static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
@@ -4206,10 +4562,27 @@ static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
     int64_t wgs = (s->n_blocks + 3) / 4;            // one wave per block
     int grid = (int)(wgs < 8192 ? wgs : 8192);     // grid-stride beyond
     if (grid < 1) grid = 1;
-    HIP_TRY(s, hipEventRecord(s->ev_start, s->stream));
     const bool en_values = (flags & KF_NEED_VALUES) != 0;
     const bool en_preds = n_preds > 0;
     const bool en_groups = groups != nullptr;
+    // the closed-form scan of a part too large for the last-level cache
+    // (or a forced policy) reads its dense streams past the caches, and
+    // the nibble-packed copy where a block has one (BYDB_PACK_ON takes the
+    // streaming kernels for any size: only they read packed data).  The
+    // copy is built here, ahead of ev_start, so the timing brackets the
+    // scan only.
+    const bool streaming =
+        !en_values && !en_preds && !en_groups &&
+        (s->field_pack == BYDB_PACK_ON ||
+         bydb_stream_policy_pick(s->stream_policy, s->payload_len) ==
+             BYDB_STREAM_STREAMING);
+    const uint8_t *pack = nullptr;
+    if (streaming && pack_wanted(s)) {
+        int rc = pack_build(s);
+        if (rc != BYDB_OK) return rc;
+        pack = s->d_pack;
+    }
+    HIP_TRY(s, hipEventRecord(s->ev_start, s->stream));
     using ScanFn = decltype(&k_scan_agg_t<false, false, false, false, false>);
     ScanFn kfn, kfn_walk = nullptr;
     // the clamp-free instantiations run when the query range covers the
@@ -4245,11 +4618,7 @@ static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
         BYDB_KSEL(false)
     }
 #undef BYDB_KSEL
-    // the closed-form scan of a part too large for the last-level cache
-    // (or a forced policy) reads its dense streams past the caches
-    if (!en_values && !en_preds && !en_groups &&
-        bydb_stream_policy_pick(s->stream_policy, s->payload_len) ==
-            BYDB_STREAM_STREAMING)
+    if (streaming)
         kfn = en_clamp
                   ? k_scan_agg_t<false, false, false, false, true, true>
                   : k_scan_agg_t<false, false, false, false, false, true>;
@@ -4261,7 +4630,7 @@ static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
                            groups, s->d_gmap, s->d_gruns, s->n_gslots,
                            s->gmul[0], s->gmul[1], s->gmul[2],
                            (int64_t)s->n_groups, s->d_acc, s->d_err,
-                           walk_count, s->d_first_seen);
+                           walk_count, s->d_first_seen, pack);
         return hipGetLastError();
     };
     // light pass: every block whose predicate verdict is uniform (no

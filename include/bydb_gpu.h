@@ -434,6 +434,66 @@ int bydb_set_stream_policy(bydb_session *s, int policy);
  * BYDB_ERR_BAD_ARG for an unknown policy. */
 int bydb_stream_policy_pick(int policy, uint64_t payload_bytes);
 
+/* ---- nibble-packed dense field streams ----
+ * A dense one-byte delta stream whose deltas all lie in [-8, 7] (zigzag
+ * bytes <= 15) carries four bits per byte.  Parts are immutable and stay
+ * resident, so the session keeps a 4-bit copy of such streams and the
+ * closed-form streaming scan (sum/count, no predicate, no tag group-by,
+ * the kernels BYDB_STREAM_STREAMING selects) reads it in place of the byte
+ * stream for every block it folds whole: half the bytes.  A block cut by
+ * the timestamp clamp, and every other kind of scan, reads the byte stream.
+ * Results do not depend on the mode.
+ *
+ * The copy is derived state over the resident part, like the dedup
+ * survivors: built on the first consume that reads it (that consume waits
+ * once for the build), rebuilt after bydb_part_reserve / bydb_part_append,
+ * freed by bydb_part_reserve, by a change of mode and with the session.  It
+ * costs device memory: up to half the dense
+ * field bytes again, plus four bytes per block.
+ *
+ * A block is a CANDIDATE when field_enc == BYDB_ENC_DELTA, 2 <= count <=
+ * 8192, field_len == count - 1 and the field stream is not in the sidecar.
+ * Every candidate gets a slot; the build fills it if every byte of the
+ * stream is <= 15, otherwise the block stays unpacked and the slot is
+ * wasted.
+ *
+ * AUTO (default): pack when the stream-load policy resolves to streaming
+ * for the session (bydb_stream_policy_pick(...) == BYDB_STREAM_STREAMING);
+ * a part that fits the last-level cache is bound by a memory round trip,
+ * not by bandwidth.  If the arena cannot be allocated the scan reads the
+ * byte streams: no error, and the stats show no packed block.
+ * OFF: never read (and never build) the copy.
+ * A call that changes the mode frees the copy; the first consume that reads
+ * packed data under the new mode builds it again.
+ * ON: pack for any size; the closed-form scan then takes the streaming
+ * kernels whatever the stream-load policy says, since only they read packed
+ * data.  If the arena cannot be allocated the consume returns BYDB_ERR_OOM
+ * naming the size; the session stays usable, unpacked.
+ * BYDB_ERR_BAD_ARG (session stays usable) for any other value. */
+enum { BYDB_PACK_AUTO = 0, BYDB_PACK_OFF = 1, BYDB_PACK_ON = 2 };
+int bydb_set_field_pack(bydb_session *s, int mode);
+
+/* What the build did: out[0] candidate blocks, out[1] packed blocks, out[2]
+ * packed payload bytes (ceil((count-1)/2) per packed block), out[3] bytes
+ * of the slot arena (the slot table's 4 bytes per block come on top).
+ * Valid after the first consume that built the copy; all zero before that,
+ * whenever the current mode and stream-load policy would not read packed
+ * data (OFF; AUTO on a part the policy resolves to cached), and out[1..3]
+ * when nothing could be packed. */
+int bydb_field_pack_stats(bydb_session *s, uint64_t out[4]);
+
+/* Pure host, no GPU, no session: the slot planner of the build.  Candidate
+ * block i gets slot_len[i] = ceil((count-1)/2) rounded up to a multiple of
+ * 128 bytes at slot_off[i], a multiple of 128; slots are laid end to end in
+ * block order, so they are pairwise disjoint and share no 128-byte memory
+ * line, and a full 8192-row block takes exactly 4 KiB.  Other blocks get
+ * slot_len 0 (slot_off 0).  *arena_bytes is the sum of the slots.
+ * BYDB_ERR_BAD_ARG on null outputs. */
+int bydb_field_pack_plan(const bydb_block_desc *blocks, int64_t n_blocks,
+                         uint64_t *slot_off /* n_blocks */,
+                         uint32_t *slot_len /* n_blocks */,
+                         uint64_t *arena_bytes);
+
 /* Timing of the last consume's kernels in milliseconds (HIP events on the
  * session stream) — feeds bench.py's roofline.achieved. */
 double bydb_last_consume_ms(bydb_session *s);
