@@ -83,6 +83,27 @@ OP_EQ, OP_NE, OP_LT, OP_GT, OP_LE, OP_GE = 1, 2, 3, 4, 5, 6
 OP_IN, OP_NOT_IN = 9, 10
 TAG_STRING, TAG_INT = 1, 2
 FILTER_MAX_CONDS = 8
+TOP_ROWS_MAX = 1024
+
+
+class TopRow(C.Structure):
+    """One data point of a raw-row top-N (bydb_top_row).  value_i: the int64
+    value, or a float64 row's decimal mantissa in its own block's exponent;
+    value_f: the restored float64 (0.0 for int64 fields); seq: storage order,
+    (block << 13) | row."""
+    _fields_ = [
+        ("series_id", C.c_uint64),
+        ("ts", C.c_int64),
+        ("version", C.c_int64),
+        ("value_i", C.c_int64),
+        ("value_f", C.c_double),
+        ("seq", C.c_uint64),
+    ]
+
+    def astuple(self):
+        return (self.series_id, self.ts, self.version, self.value_i,
+                self.value_f, self.seq)
+
 FILTER_MAX_VALUES = 4096
 
 
@@ -368,6 +389,16 @@ def _load():
     lib.bydb_group_first_seen.restype = C.c_int
     lib.bydb_group_first_seen.argtypes = [C.c_void_p, C.POINTER(C.c_uint64),
                                           C.c_int64]
+    lib.bydb_top_configure.restype = C.c_int
+    lib.bydb_top_configure.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int]
+    lib.bydb_top_finalize.restype = C.c_int
+    lib.bydb_top_finalize.argtypes = [C.c_void_p, C.POINTER(TopRow), C.c_int64,
+                                      C.POINTER(C.c_int64)]
+    lib.bydb_top_rows_merge.restype = C.c_int
+    lib.bydb_top_rows_merge.argtypes = [C.POINTER(C.POINTER(TopRow)),
+                                        C.POINTER(C.c_int64), C.c_int, C.c_int,
+                                        C.c_int64, C.c_int, C.POINTER(TopRow),
+                                        C.POINTER(C.c_int64)]
     lib.bydb_reduce_partials2.restype = C.c_int
     lib.bydb_reduce_partials2.argtypes = [C.POINTER(Partial), C.c_int64, C.c_int64,
                                           C.c_int, C.c_int16, C.POINTER(Result)]
@@ -680,6 +711,26 @@ class Session:
             len(slots), blob_ptrs, off_ptrs, nvals, mode))
         self._ck(_lib.bydb_set_float_exp(self._h, float_exp))
 
+    def configure_top(self, field_vtype, n, asc=False, float_exp=0):
+        """Make the session a raw-row BatchTop operator (top.go:30-199): the
+        next consume selects the n highest (asc: lowest) field values among
+        the rows it would have aggregated; top_rows() returns them.  Equal
+        values surface in storage order.  configure*() switches back."""
+        self._ck(_lib.bydb_set_float_exp(self._h, float_exp))
+        self._ck(_lib.bydb_top_configure(self._h, field_vtype, n,
+                                         1 if asc else 0))
+        self.n_groups = 1
+        self.field_vtype = field_vtype
+        self.top_n = n
+
+    def top_rows(self):
+        """Finalize a top epoch: at most n TopRow, best first."""
+        cap = max(int(self.top_n), 1)
+        out = (TopRow * cap)()
+        got = C.c_int64(0)
+        self._ck(_lib.bydb_top_finalize(self._h, out, cap, C.byref(got)))
+        return [out[i] for i in range(got.value)]
+
     def set_partials_buffer(self, dev_ptr, nbytes):
         self._ck(_lib.bydb_set_partials_buffer(self._h, dev_ptr, nbytes))
 
@@ -802,6 +853,24 @@ def reduce_partials(parts_flat, n_parts_per_group, n_groups, field_vtype,
     if rc != 0:
         raise RuntimeError(f"reduce_partials rc={rc}")
     return list(out)
+
+
+def top_rows_merge(lists, field_vtype, n, asc=False):
+    """Host reduce side of a sharded raw-row top-N: a stable N-way merge of
+    per-shard top_rows() results (lists of TopRow).  On equal values the
+    earlier list wins, then the smaller seq."""
+    arrs = [(TopRow * max(len(l), 1))(*l) for l in lists]
+    ptrs = (C.POINTER(TopRow) * max(len(lists), 1))(
+        *[C.cast(a, C.POINTER(TopRow)) for a in arrs])
+    lens = (C.c_int64 * max(len(lists), 1))(*[len(l) for l in lists])
+    total = sum(len(l) for l in lists)
+    out = (TopRow * max(min(total, max(n, 0)), 1))()
+    got = C.c_int64(0)
+    rc = _lib.bydb_top_rows_merge(ptrs, lens, len(lists), field_vtype, n,
+                                  1 if asc else 0, out, C.byref(got))
+    if rc != 0:
+        raise RuntimeError(f"top_rows_merge rc={rc}")
+    return [out[i] for i in range(got.value)]
 
 
 def i64_tag_cell(v: int) -> bytes:

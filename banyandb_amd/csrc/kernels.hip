@@ -249,6 +249,8 @@ enum {
                             // the configured session exponent (per-block
                             // rescale is a later row; silent mixing would
                             // corrupt sums and make min/max incomparable)
+    DERR_TOP_NULL = 7,      // a top-rows consume selected a row of a
+                            // null-bearing (Plain) field block
 };
 
 __device__ __forceinline__ void dev_set_err(DevErr *e, unsigned code, uint64_t bi) {
@@ -3799,6 +3801,625 @@ __global__ __launch_bounds__(WAVE) void k_pack_fields(
     }
 }
 
+// ---------------- BatchTop over raw rows ----------------
+// A measure query with `top` and no `agg` runs measure.BatchTop over every
+// data point the scan yields (pkg/query/vectorized/measure/plan/
+// analyzer.go:118-151, plan/top.go:28-46, top.go:30-199): a whole-result
+// top-N by field value, equal values in input order.  Input order is storage
+// order, seq = (block << 13) | row.
+//
+// The top rows lie in few blocks.  Give every block the key "its best
+// selected value" and order blocks by (key, best first; index ascending).
+// Every row of the true top-N lies in one of the N best blocks: were a row r
+// of block B outside them, N other blocks would each hold a row that beats r
+// (a better value, or the same value in a smaller block index and so a
+// smaller seq).  Two exact selections are therefore enough — the N best
+// blocks (k_top_bounds + top_select), then the N best rows inside those
+// blocks (k_top_row_keys + top_select) — and no buffer grows with the data.
+//
+// Keys are order-preserving uint64: a larger key is better in both
+// directions.  float64 mantissas are rescaled exactly to the session
+// exponent first (the rescale WavePartial::add does for min/max).
+#define TOP_BLOCK_ROWS 8192   // rows per block, at most (measure.go:41-46)
+#define TOP_CHUNK 1024        // selector chunk: 256 threads x 4 entries
+
+__host__ __device__ __forceinline__ uint64_t top_key(int64_t v, bool asc) {
+    uint64_t k = (uint64_t)v ^ (1ull << 63);
+    return asc ? ~k : k;
+}
+
+__host__ __device__ __forceinline__ int64_t top_unkey(uint64_t k, bool asc) {
+    if (asc) k = ~k;
+    return (int64_t)(k ^ (1ull << 63));
+}
+
+// What the scan's preamble decides for one block: the clamped rows
+// [r0, r1], the float rescale and the row-varying walkers.
+struct TopSel {
+    int64_t r0, r1;
+    int fdiff;
+    PredWalk pw[3];
+    PredWalk *wp[3];
+};
+
+// The preamble of k_scan_agg_t, restated in two halves (sharing it through
+// a device function would have to change the scan kernel).  The first half:
+// count and exponent checks and the FindRange row clamp.  Returns false when
+// the block selects nothing (or erred).  A Plain field block skips the
+// exponent check: the callers reject it once rows are selected.
+// It calls clamp_count_stream, an out-of-line function the scan's clamped
+// instantiations share, all of them __launch_bounds__(256, 4).  The compiler
+// derives such a function's register budget from the kernels that call it,
+// so only kernels with those launch bounds may call top_clamp: from a
+// 64-thread kernel it moved the scan instantiations' spill counts
+// (profiles/top_rows.txt).
+__device__ __forceinline__ bool top_clamp(
+    const uint8_t *__restrict__ payload, const bydb_block_desc *bd, int64_t bi,
+    int64_t min_ts, int64_t max_ts, int flags, int lane, DevErr *derr,
+    TopSel *ts) {
+    const int64_t n = (int64_t)bd->count;
+    const int64_t ts_min = bd->ts_min, ts_max = bd->ts_max;
+    ts->fdiff = 0;
+    if (n < 1 || n > TOP_BLOCK_ROWS) {
+        dev_set_err(derr, DERR_BAD_ENC, (uint64_t)bi);
+        return false;
+    }
+    if ((flags & KF_FLOAT) && bd->field_enc != BYDB_ENC_PLAIN) {
+        int16_t cfge = (int16_t)(uint16_t)((uint32_t)flags >> 16);
+        ts->fdiff = (int)bd->exp - (int)cfge;
+        if (ts->fdiff < 0 || ts->fdiff > 18) {
+            dev_set_err(derr, DERR_EXP_MISMATCH, (uint64_t)bi);
+            return false;
+        }
+    }
+    // ---- row clamp (timestamp.FindRange, range.go:143-170) ----
+    int64_t r0 = 0, r1 = n - 1;
+    if (ts_min > ts_max) {
+        dev_set_err(derr, DERR_DESC_TS, (uint64_t)bi);
+        return false;
+    }
+    if (!(min_ts <= ts_min && max_ts >= ts_max)) {
+        if (ts_min > max_ts || ts_max < min_ts) return false;
+        uint8_t tenc = bd->ts_enc_with_version;
+        uint8_t tc = tenc >= BYDB_ENC_CONST_WV &&
+                             tenc <= BYDB_ENC_DELTA_OF_DELTA_WV
+                         ? tenc - 4 : tenc;
+        const uint8_t *tstream = payload + bd->ts_off;
+        if (tc == BYDB_ENC_CONST) {
+            // all == ts_min; overlap already implies in-range
+        } else if (tc == BYDB_ENC_DELTA_CONST) {
+            int vl;
+            int64_t dd = decode_one_varint(tstream, &vl);
+            if (dd <= 0) {
+                dev_set_err(derr, DERR_DESC_TS, (uint64_t)bi);
+                return false;
+            }
+            if (min_ts > ts_min) r0 = (min_ts - ts_min + dd - 1) / dd;
+            if (max_ts < ts_max) r1 = (max_ts - ts_min) / dd;
+            if (r1 > n - 1) r1 = n - 1;
+        } else if (tc == BYDB_ENC_DELTA || tc == BYDB_ENC_DELTA_OF_DELTA) {
+            bool dod = tc == BYDB_ENC_DELTA_OF_DELTA;
+            const uint8_t *s = tstream;
+            int64_t d1 = 0;
+            if (dod) {
+                int vl;
+                d1 = decode_one_varint(s, &vl);
+                s += vl;
+            }
+            int64_t row1 = (int64_t)((uint64_t)ts_min + (uint64_t)d1);
+            uint64_t nlo, nhi;
+            clamp_count_stream(s, n - 1, dod, dod ? row1 : ts_min, d1, min_ts,
+                               max_ts, lane, &nlo, &nhi, derr, (uint64_t)bi);
+            if (ts_min < min_ts) nlo++;
+            if (ts_min > max_ts) nhi++;
+            if (dod) {
+                if (row1 < min_ts) nlo++;
+                if (row1 > max_ts) nhi++;
+            }
+            r0 = (int64_t)nlo;
+            r1 = n - 1 - (int64_t)nhi;
+        }
+        if (r0 > r1) return false;
+    }
+    ts->r0 = r0;
+    ts->r1 = r1;
+    return true;
+}
+
+// The second half: tag predicates and dedup survivors — the flag byte, then
+// the walkers.  Nothing here leaves the kernel (every helper is inlined).
+__device__ __forceinline__ bool top_walkers(
+    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
+    int64_t bi, int64_t n_blocks, const PredBlock *__restrict__ preds,
+    int n_preds, const uint64_t *__restrict__ pred_bm,
+    const uint8_t *__restrict__ pred_flags, DevErr *derr, TopSel *ts) {
+    ts->wp[0] = ts->wp[1] = ts->wp[2] = nullptr;
+    if (preds != nullptr) {
+        const uint8_t pf = pred_flags[bi];
+        if (pf == PF_SKIP) return false;
+        if (pf == PF_ERR) {
+            dev_set_err(derr, DERR_BAD_ENC, (uint64_t)bi);
+            return false;
+        }
+        if (pf == PF_WALK) {
+            bool skip_block = false;
+#pragma unroll
+            for (int sl = 0; sl < 3; sl++) {
+                if (sl >= n_preds || skip_block) continue;
+                PredBlock pb = preds[(int64_t)sl * n_blocks + bi];
+                if (pb.disabled) continue;
+                if (!pb.active) { skip_block = true; continue; }
+                PredWalk *w = &ts->pw[sl];
+                pred_init(w, payload, sidecar, &pb, pred_bm);
+                if (pb.uniform) {
+                    pred_advance(w);
+                    if (!w->run_match) skip_block = true;
+                } else {
+                    ts->wp[sl] = w;
+                }
+            }
+            if (skip_block) return false;
+        }
+    }
+    return true;
+}
+
+// Does any row of [r0, r1] pass the walkers?  (Plain blocks only: the fold
+// is never run on them.)
+__device__ __forceinline__ bool top_any_row(TopSel *ts, int lane) {
+    bool any = false;
+    for (int64_t base = ts->r0; base <= ts->r1; base += WAVE) {
+        int64_t row = base + lane;
+        bool need = row <= ts->r1;
+        bool ok = walkers_match(ts->wp[0], ts->wp[1], ts->wp[2], row, need) &&
+                  need;
+        any = any || __any(ok);
+    }
+    return any;
+}
+
+// Stage 1 — one wave per block, grid-stride: the key of the block's best
+// selected value and a validity byte (pre-zeroed by the host).  It reads
+// what a MIN/MAX scan over the same selection reads: the field fold is the
+// scan's own, fold_rows<true, false, DENSE_CALL> with values requested.
+// (launch bounds: those of the scan's clamped value instantiations, whose
+// out-of-line helpers this kernel calls — see top_clamp)
+__global__ __launch_bounds__(256, 4) void k_top_bounds(
+    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
+    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
+    int64_t min_ts, int64_t max_ts, int flags, int asc,
+    const PredBlock *__restrict__ preds, int n_preds,
+    const uint64_t *__restrict__ pred_bm,
+    const uint8_t *__restrict__ pred_flags, uint64_t *__restrict__ keys,
+    uint8_t *__restrict__ valid, DevErr *derr) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave_id =
+        (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t bi = wave_id; bi < n_blocks; bi += n_waves) {
+        const bydb_block_desc *bd = &blocks[bi];
+        TopSel ts;
+        if (!top_clamp(payload, bd, bi, min_ts, max_ts, flags, lane, derr,
+                       &ts) ||
+            !top_walkers(payload, sidecar, bi, n_blocks, preds, n_preds,
+                         pred_bm, pred_flags, derr, &ts))
+            continue;
+        const uint8_t fenc = bd->field_enc;
+        if (fenc == BYDB_ENC_PLAIN) {
+            // null-bearing block: never drop a null row silently
+            if (top_any_row(&ts, lane))
+                dev_set_err(derr, DERR_TOP_NULL, (uint64_t)bi);
+            continue;
+        }
+        const RowFold f = fold_rows<true, false, DENSE_CALL>(
+            payload + bd->field_off, nullptr, fenc, bd->field_first,
+            bd->field_len, (int64_t)bd->count, ts.r0, ts.r1, true, false,
+            lane, ts.wp[0], ts.wp[1], ts.wp[2], derr, (uint64_t)bi);
+        if (f.cnt == 0 || !f.have_mm) continue;
+        int64_t mn = f.mn, mx = f.mx;
+        if (ts.fdiff) {
+            const int64_t mfac = c_pow10i[ts.fdiff];
+            if (__builtin_mul_overflow(mn, mfac, &mn) ||
+                __builtin_mul_overflow(mx, mfac, &mx)) {
+                dev_set_err(derr, DERR_EXP_MISMATCH, (uint64_t)bi);
+                continue;
+            }
+        }
+        if (lane == 0) {
+            keys[bi] = top_key(asc ? mn : mx, asc != 0);
+            valid[bi] = 1;
+        }
+    }
+}
+
+// ---- top_select: the N best of n entries, entirely on the device ----
+// Best = key descending, index ascending; emitted in ascending index order.
+// An MSB radix select fixes the N-th best key one byte per pass (an LDS
+// histogram over the entries that match the prefix so far, then a pick that
+// fixes the next digit and the remaining rank); a stable compaction then
+// takes every greater entry and the first `remaining` equal ones.  Fewer
+// than N valid entries selects them all.
+struct TopSelState {
+    uint64_t prefix;      // the digits fixed so far; after 8 passes the key
+    uint32_t remaining;   // entries to take among those that match prefix
+    uint32_t all;         // at most N valid entries: take every one
+    uint32_t n_out;       // entries selected (written by k_sel_scan)
+    uint32_t _p;
+    uint32_t hist[256];
+};
+
+__global__ __launch_bounds__(256) void k_sel_hist(
+    const uint64_t *__restrict__ keys, const uint8_t *__restrict__ valid,
+    uint64_t n, TopSelState *st, int pass) {
+    __shared__ uint32_t h[256];
+    if (pass > 0 && st->all) return;
+    const uint64_t prefix = st->prefix;
+    const uint64_t mask = pass == 0 ? 0ull : ~0ull << (64 - 8 * pass);
+    const int shift = 56 - 8 * pass;
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n;
+         i += (uint64_t)gridDim.x * 256) {
+        if (!valid[i]) continue;
+        const uint64_t k = keys[i];
+        if ((k & mask) == prefix) atomicAdd(&h[(k >> shift) & 255], 1u);
+    }
+    __syncthreads();
+    if (h[threadIdx.x]) atomicAdd(&st->hist[threadIdx.x], h[threadIdx.x]);
+}
+
+// One workgroup of 256.  Pass 0 also decides `all`.  Invariant: the entries
+// that match the prefix number at least `remaining`.
+__global__ __launch_bounds__(256) void k_sel_pick(TopSelState *st, int pass,
+                                                  uint32_t want) {
+    __shared__ uint32_t h[256];
+    h[threadIdx.x] = st->hist[threadIdx.x];
+    st->hist[threadIdx.x] = 0;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    if (pass == 0) {
+        uint64_t total = 0;
+        for (int b = 0; b < 256; b++) total += h[b];
+        st->prefix = 0;
+        st->remaining = want;
+        st->all = total <= (uint64_t)want;
+        st->n_out = 0;
+    }
+    if (st->all) return;
+    uint32_t rem = st->remaining, cum = 0;
+    int digit = 0;
+    for (int b = 255; b >= 0; b--) {
+        if (cum + h[b] >= rem) { digit = b; break; }
+        cum += h[b];
+    }
+    st->prefix |= (uint64_t)digit << (56 - 8 * pass);
+    st->remaining = rem - cum;
+}
+
+// class of entry i against the selected threshold: 2 greater (always
+// taken), 1 equal (taken while the rank lasts), 0 neither
+__device__ __forceinline__ uint32_t sel_class(const uint64_t *keys,
+                                              const uint8_t *valid, uint64_t i,
+                                              uint64_t n, uint64_t thr,
+                                              bool all) {
+    if (i >= n || !valid[i]) return 0;
+    if (all) return 2;
+    const uint64_t k = keys[i];
+    return k > thr ? 2 : k == thr ? 1 : 0;
+}
+
+// per-chunk counts of greater and equal entries
+__global__ __launch_bounds__(256) void k_sel_count(
+    const uint64_t *__restrict__ keys, const uint8_t *__restrict__ valid,
+    uint64_t n, const TopSelState *st, uint32_t *__restrict__ cnt_gt,
+    uint32_t *__restrict__ cnt_eq) {
+    __shared__ uint32_t s_gt, s_eq;
+    if (threadIdx.x == 0) { s_gt = 0; s_eq = 0; }
+    __syncthreads();
+    const uint64_t thr = st->prefix;
+    const bool all = st->all != 0;
+    const uint64_t i0 = (uint64_t)blockIdx.x * TOP_CHUNK + threadIdx.x * 4;
+    uint32_t g = 0, e = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        uint32_t c = sel_class(keys, valid, i0 + k, n, thr, all);
+        g += c == 2;
+        e += c == 1;
+    }
+    if (g) atomicAdd(&s_gt, g);
+    if (e) atomicAdd(&s_eq, e);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        cnt_gt[blockIdx.x] = s_gt;
+        cnt_eq[blockIdx.x] = s_eq;
+    }
+}
+
+// One workgroup of 1024 over all chunks, in place: cnt_eq[c] becomes the
+// equal entries before chunk c, cnt_gt[c] the selected entries before it.
+__global__ __launch_bounds__(1024) void k_sel_scan(
+    TopSelState *st, uint32_t *__restrict__ cnt_gt,
+    uint32_t *__restrict__ cnt_eq, uint32_t n_chunks) {
+    __shared__ uint32_t part[1024];
+    const uint32_t per = (n_chunks + 1023) / 1024;
+    const uint32_t c0 = threadIdx.x * per;
+    const uint32_t c1 = c0 + per < n_chunks ? c0 + per : n_chunks;
+    const uint32_t rem = st->all ? 0 : st->remaining;
+    auto excl = [&](uint32_t mine) -> uint32_t {
+        part[threadIdx.x] = mine;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t run = 0;
+            for (int t = 0; t < 1024; t++) {
+                uint32_t v = part[t];
+                part[t] = run;
+                run += v;
+            }
+        }
+        __syncthreads();
+        uint32_t r = part[threadIdx.x];
+        __syncthreads();
+        return r;
+    };
+    uint32_t sum = 0;
+    for (uint32_t c = c0; c < c1; c++) sum += cnt_eq[c];
+    uint32_t run = excl(sum);
+    sum = 0;
+    for (uint32_t c = c0; c < c1; c++) {
+        const uint32_t e = cnt_eq[c];
+        const uint32_t left = rem > run ? rem - run : 0;
+        const uint32_t sel = cnt_gt[c] + (e < left ? e : left);
+        cnt_eq[c] = run;
+        cnt_gt[c] = sel;
+        run += e;
+        sum += sel;
+    }
+    run = excl(sum);
+    for (uint32_t c = c0; c < c1; c++) {
+        const uint32_t sel = cnt_gt[c];
+        cnt_gt[c] = run;
+        run += sel;
+    }
+    if (threadIdx.x == 1023) st->n_out = run;
+}
+
+// exclusive scan of one value per thread over a workgroup of 256
+__device__ __forceinline__ uint32_t sel_block_scan(uint32_t v, uint32_t *w4) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t incl = (uint32_t)wave_incl_scan32((int32_t)v, lane);
+    if (lane == 63) w4[w] = incl;
+    __syncthreads();
+    uint32_t base = 0;
+    for (int i = 0; i < 4; i++)
+        if (i < w) base += w4[i];
+    __syncthreads();
+    return base + incl - v;
+}
+
+// in-order emit: out[] receives the selected indices, ascending
+__global__ __launch_bounds__(256) void k_sel_emit(
+    const uint64_t *__restrict__ keys, const uint8_t *__restrict__ valid,
+    uint64_t n, const TopSelState *st, const uint32_t *__restrict__ sel_before,
+    const uint32_t *__restrict__ eq_before, uint32_t *__restrict__ out,
+    uint32_t out_cap) {
+    __shared__ uint32_t w4[4];
+    const uint64_t thr = st->prefix;
+    const bool all = st->all != 0;
+    const uint32_t rem = all ? 0 : st->remaining;
+    const uint64_t i0 = (uint64_t)blockIdx.x * TOP_CHUNK + threadIdx.x * 4;
+    uint32_t cls[4], e = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        cls[k] = sel_class(keys, valid, i0 + k, n, thr, all);
+        e += cls[k] == 1;
+    }
+    uint32_t eq_rank = eq_before[blockIdx.x] + sel_block_scan(e, w4);
+    uint32_t s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (cls[k] == 1) cls[k] = eq_rank++ < rem ? 2 : 0;
+        s += cls[k] == 2;
+    }
+    uint32_t at = sel_before[blockIdx.x] + sel_block_scan(s, w4);
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (cls[k] == 2) {
+            if (at < out_cap) out[at] = (uint32_t)(i0 + k);
+            at++;
+        }
+}
+
+// Stage 3a — one wave per chosen block: [r0, r1] recomputed, packed as
+// r0 | r1 << 16 (TOP_NO_ROWS: nothing selected).  A kernel of its own for
+// its launch bounds (see top_clamp); stage 3b decodes with the dedup
+// build's out-of-line helpers, which belong to 64-thread kernels.
+#define TOP_NO_ROWS 0xFFFFFFFFu
+__global__ __launch_bounds__(256, 4) void k_top_row_range(
+    const uint8_t *__restrict__ payload,
+    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
+    int64_t min_ts, int64_t max_ts, int flags, const TopSelState *st,
+    const uint32_t *__restrict__ chosen, uint32_t *__restrict__ range,
+    uint32_t cap, DevErr *derr) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (c >= st->n_out || c >= cap) return;
+    const int64_t bi = (int64_t)chosen[c];
+    TopSel ts;
+    uint32_t r = TOP_NO_ROWS;
+    if (bi < n_blocks && top_clamp(payload, &blocks[bi], bi, min_ts, max_ts,
+                                   flags, lane, derr, &ts))
+        r = (uint32_t)ts.r0 | ((uint32_t)ts.r1 << 16);
+    if (lane == 0) range[c] = r;
+}
+
+// Stage 3b — one wave per chosen block (at most N, ascending block index):
+// the field column decoded into the block's slot of the row grid, then every
+// selected row's value replaced by its key.  The grid is chosen x 8192,
+// block-major, so index order is seq order; rvalid is pre-zeroed.
+__global__ __launch_bounds__(WAVE) void k_top_row_keys(
+    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
+    uint64_t limit, const bydb_block_desc *__restrict__ blocks,
+    int64_t n_blocks, int flags, int asc,
+    const PredBlock *__restrict__ preds, int n_preds,
+    const uint64_t *__restrict__ pred_bm,
+    const uint8_t *__restrict__ pred_flags, const TopSelState *st,
+    const uint32_t *__restrict__ chosen, const uint32_t *__restrict__ range,
+    uint64_t *__restrict__ grid, uint8_t *__restrict__ rvalid, DevErr *derr) {
+    const int lane = threadIdx.x;
+    const uint32_t c = blockIdx.x;
+    if (c >= st->n_out) return;
+    const int64_t bi = (int64_t)chosen[c];
+    if (bi >= n_blocks || range[c] == TOP_NO_ROWS) return;
+    const bydb_block_desc *bd = &blocks[bi];
+    TopSel ts;
+    ts.r0 = (int64_t)(range[c] & 0xFFFFu);
+    ts.r1 = (int64_t)(range[c] >> 16);
+    ts.fdiff = 0;
+    if (flags & KF_FLOAT)   // in 0..18: top_clamp accepted the block
+        ts.fdiff = (int)bd->exp - (int)(int16_t)(uint16_t)((uint32_t)flags >> 16);
+    if (!top_walkers(payload, sidecar, bi, n_blocks, preds, n_preds, pred_bm,
+                     pred_flags, derr, &ts))
+        return;
+    const uint8_t fenc = bd->field_enc;
+    const int64_t n = (int64_t)bd->count;
+    int64_t *vals = (int64_t *)(grid + (uint64_t)c * TOP_BLOCK_ROWS);
+    uint8_t *ok_out = rvalid + (uint64_t)c * TOP_BLOCK_ROWS;
+    if (fenc == BYDB_ENC_CONST) {
+        for (int64_t i = lane; i < n; i += WAVE) vals[i] = bd->field_first;
+    } else if (fenc == BYDB_ENC_DELTA_CONST || fenc == BYDB_ENC_DELTA ||
+               fenc == BYDB_ENC_DELTA_OF_DELTA) {
+        if (bd->field_off & TAG_SIDECAR_BIT) {
+            dev_set_err(derr, DERR_BAD_ENC, (uint64_t)bi);
+            return;
+        }
+        dedup_decode_list(payload, bd->field_off, limit, fenc, bd->field_first,
+                          n, false, lane, vals, derr, (uint64_t)bi);
+    } else {
+        return;   // Plain blocks never carry a valid bound
+    }
+    // the decode stores a row from whichever lane held its terminator
+    __threadfence();
+    const int64_t mfac = c_pow10i[ts.fdiff];
+    for (int64_t base = ts.r0; base <= ts.r1; base += WAVE) {
+        const int64_t row = base + lane;
+        const bool need = row <= ts.r1;
+        const bool ok =
+            walkers_match(ts.wp[0], ts.wp[1], ts.wp[2], row, need) && need;
+        if (ok) {
+            int64_t v = vals[row];
+            if (ts.fdiff && __builtin_mul_overflow(v, mfac, &v)) {
+                dev_set_err(derr, DERR_EXP_MISMATCH, (uint64_t)bi);
+            } else {
+                vals[row] = (int64_t)top_key(v, asc != 0);
+                ok_out[row] = 1;
+            }
+        }
+    }
+}
+
+// One winner as the device hands it over; the host sorts the at most 1024
+// of them and restores value_f.
+struct TopRec {
+    uint64_t series_id;
+    int64_t ts, version;
+    int64_t value;      // block-domain value / mantissa
+    uint64_t key;       // session-domain order key
+    uint64_t seq;
+    int32_t exp;        // the block's decimal exponent
+    int32_t _p;
+};
+
+// Stage 5a — one thread per winner: what the key grid and the descriptor
+// hold.  It runs before 5b, which reuses the grid as decode scratch.
+__global__ __launch_bounds__(256) void k_top_resolve_keys(
+    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks, int flags,
+    int asc, const TopSelState *st_rows, const uint32_t *__restrict__ chosen,
+    const uint32_t *__restrict__ winners, const uint64_t *__restrict__ grid,
+    TopRec *__restrict__ recs, uint32_t cap) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= st_rows->n_out || i >= cap) return;
+    const uint32_t idx = winners[i];
+    const uint32_t row = idx & (TOP_BLOCK_ROWS - 1);
+    const int64_t bi = (idx >> 13) < cap ? (int64_t)chosen[idx >> 13] : n_blocks;
+    TopRec r = {};
+    r.seq = ~0ull;   // no block: stage 5b leaves the record alone
+    if (bi < n_blocks) {
+        const bydb_block_desc *bd = &blocks[bi];
+        const uint64_t key = grid[idx];
+        int64_t v = top_unkey(key, asc != 0);
+        if (flags & KF_FLOAT) {
+            int16_t cfge = (int16_t)(uint16_t)((uint32_t)flags >> 16);
+            int fdiff = (int)bd->exp - (int)cfge;
+            if (fdiff > 0 && fdiff <= 18) v /= c_pow10i[fdiff];   // exact
+        }
+        r.series_id = bd->series_id;
+        r.value = v;
+        r.key = key;
+        r.seq = ((uint64_t)bi << 13) | row;
+        r.exp = bd->exp;
+    }
+    recs[i] = r;
+}
+
+// Stage 5b — one wave per winner: the row's timestamp and version.  Const /
+// DeltaConst lists are closed form; a stream-coded list is decoded, as
+// k_dedup_decode does, into the winner's own slot of the (now free) grid.
+__global__ __launch_bounds__(WAVE) void k_top_resolve(
+    const uint8_t *__restrict__ payload, uint64_t limit,
+    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
+    const TopSelState *st_rows, uint64_t *__restrict__ grid,
+    TopRec *__restrict__ recs, DevErr *derr) {
+    const int lane = threadIdx.x;
+    const uint32_t i = blockIdx.x;
+    if (i >= st_rows->n_out) return;
+    const uint64_t seq = recs[i].seq;
+    const int64_t bi = (int64_t)(seq >> 13);
+    const int64_t row = (int64_t)(seq & (TOP_BLOCK_ROWS - 1));
+    if (bi >= n_blocks) return;
+    const bydb_block_desc *bd = &blocks[bi];
+    const int64_t n = (int64_t)bd->count;
+    if (n < 1 || n > TOP_BLOCK_ROWS || row >= n) return;
+    int64_t *scratch = (int64_t *)(grid + (uint64_t)i * TOP_BLOCK_ROWS);
+    const uint8_t tenc = bd->ts_enc_with_version;
+    const uint8_t tc = tenc >= BYDB_ENC_CONST_WV ? tenc - 4 : tenc;
+    int64_t ts = bd->ts_min;
+    if (tc == BYDB_ENC_DELTA_CONST) {
+        if (bd->ts_off + 11 > limit) {
+            dev_set_err(derr, DERR_BAD_STREAM, (uint64_t)bi);
+            return;
+        }
+        int vl;
+        int64_t dd = decode_one_varint(payload + bd->ts_off, &vl);
+        ts = (int64_t)((uint64_t)bd->ts_min + (uint64_t)row * (uint64_t)dd);
+    } else if (tc == BYDB_ENC_DELTA || tc == BYDB_ENC_DELTA_OF_DELTA) {
+        dedup_decode_list(payload, bd->ts_off, limit, tc, bd->ts_min, n, true,
+                          lane, scratch, derr, (uint64_t)bi);
+        __threadfence();
+        ts = scratch[row];
+        __threadfence();   // read before the version decode reuses the slot
+    } else if (tc != BYDB_ENC_CONST) {
+        dev_set_err(derr, DERR_BAD_ENC, (uint64_t)bi);
+        return;
+    }
+    int64_t ver = bd->version_first;
+    const uint8_t venc = bd->version_enc;
+    if (venc == BYDB_ENC_DELTA_CONST || venc == BYDB_ENC_DELTA ||
+        venc == BYDB_ENC_DELTA_OF_DELTA) {
+        dedup_decode_list(payload, bd->ts_off + bd->ts_len, limit, venc,
+                          bd->version_first, n, false, lane, scratch, derr,
+                          (uint64_t)bi);
+        __threadfence();
+        ver = scratch[row];
+    } else if (venc != BYDB_ENC_CONST) {
+        dev_set_err(derr, DERR_BAD_ENC, (uint64_t)bi);
+        return;
+    }
+    if (lane == 0) {
+        recs[i].ts = ts;
+        recs[i].version = ver;
+    }
+}
+
 // ===================== host session =====================
 
 struct bydb_session {
@@ -3891,6 +4512,25 @@ struct bydb_session {
     uint8_t *d_pack = nullptr;
     unsigned long long *d_pack_ctr = nullptr;
     uint64_t pack_stats[4] = {0, 0, 0, 0};
+    // BatchTop over raw rows (bydb_top_configure): the session selects rows
+    // instead of folding them.  Everything below is scratch of one consume;
+    // the row grid is sized once from top_n.
+    bool top_on = false;
+    int64_t top_n = 0;
+    int top_asc = 0;
+    uint64_t *d_top_bkeys = nullptr;    // [n_blocks] best-value keys
+    uint8_t *d_top_bvalid = nullptr;
+    int64_t top_blocks_cap = 0;
+    uint64_t *d_top_grid = nullptr;     // [top_n][8192] row keys
+    uint8_t *d_top_rvalid = nullptr;
+    uint32_t *d_top_chosen = nullptr;   // [top_n] block indices
+    uint32_t *d_top_winners = nullptr;  // [top_n] grid indices
+    uint32_t *d_top_range = nullptr;    // [top_n] clamped rows per chosen block
+    TopRec *d_top_recs = nullptr;       // [top_n]
+    int64_t top_grid_cap = 0;           // in blocks (= top_n it was sized for)
+    uint32_t *d_top_cnt = nullptr;      // selector chunk counters, 2 arrays
+    uint64_t top_cnt_cap = 0;           // chunks per array
+    TopSelState *d_top_st = nullptr;    // [2]: block select, row select
 };
 
 // What a read-once pass has to exceed before its loads bypass the caches:
@@ -3945,6 +4585,21 @@ static void pack_free(bydb_session *s) {
     if (s->d_pack) (void)hipFree(s->d_pack);
     s->d_pack = nullptr;
     for (int i = 0; i < 4; i++) s->pack_stats[i] = 0;
+}
+
+static void top_free(bydb_session *s) {
+    void *ptrs[] = {s->d_top_bkeys, s->d_top_bvalid, s->d_top_grid,
+                    s->d_top_rvalid, s->d_top_chosen, s->d_top_winners,
+                    s->d_top_recs, s->d_top_cnt, s->d_top_st,
+                    s->d_top_range};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    s->d_top_bkeys = nullptr; s->d_top_bvalid = nullptr;
+    s->d_top_grid = nullptr; s->d_top_rvalid = nullptr;
+    s->d_top_chosen = nullptr; s->d_top_winners = nullptr;
+    s->d_top_recs = nullptr; s->d_top_cnt = nullptr; s->d_top_st = nullptr;
+    s->d_top_range = nullptr;
+    s->top_blocks_cap = 0; s->top_grid_cap = 0; s->top_cnt_cap = 0;
 }
 
 extern "C" bydb_session *bydb_session_create(int device) {
@@ -4003,6 +4658,7 @@ extern "C" void bydb_session_destroy(bydb_session *s) {
     if (s->d_first_seen) (void)hipFree(s->d_first_seen);
     dedup_free(s);
     pack_free(s);
+    top_free(s);
     if (s->d_pack_ctr) (void)hipFree(s->d_pack_ctr);
     if (s->ev_start) (void)hipEventDestroy(s->ev_start);
     if (s->ev_stop) (void)hipEventDestroy(s->ev_stop);
@@ -4184,6 +4840,7 @@ extern "C" int bydb_agg_configure(bydb_session *s, int field_vtype,
                                   int mode) {
     HIP_TRY(s, hipSetDevice(s->device));
     if (n_groups < 1) { s->err = "n_groups < 1"; return BYDB_ERR_BAD_ARG; }
+    s->top_on = false;   // a BatchAggregation operator again
     s->field_vtype = field_vtype;
     s->func_mask = func_mask;
     s->n_groups = n_groups;
@@ -4896,6 +5553,135 @@ static int ensure_pred_bm(bydb_session *s, uint64_t words) {
     return BYDB_OK;
 }
 
+// ---- BatchTop over raw rows: the pipeline of one consume ----
+// (header: "top-N data points by field value"; kernels: k_top_bounds,
+// k_sel_*, k_top_row_keys, k_top_resolve*)
+
+template <typename T>
+static int top_alloc(bydb_session *s, T **p, uint64_t count) {
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+    HIP_TRY(s, hipMalloc(p, sizeof(T) * (size_t)(count ? count : 1)));
+    return BYDB_OK;
+}
+
+// top_select(keys, valid, n, want) -> out[], count in st->n_out.  Nothing
+// comes back to the host.
+static int top_select(bydb_session *s, const uint64_t *keys,
+                      const uint8_t *valid, uint64_t n, uint32_t want,
+                      TopSelState *st, uint32_t *out) {
+    const uint64_t chunks = (n + TOP_CHUNK - 1) / TOP_CHUNK;
+    uint32_t *cnt_gt = s->d_top_cnt, *cnt_eq = s->d_top_cnt + s->top_cnt_cap;
+    const int hgrid = (int)(chunks < 2048 ? chunks : 2048);
+    HIP_TRY(s, hipMemsetAsync(st, 0, sizeof(TopSelState), s->stream));
+    for (int pass = 0; pass < 8; pass++) {
+        hipLaunchKernelGGL(k_sel_hist, dim3(hgrid), dim3(256), 0, s->stream,
+                           keys, valid, n, st, pass);
+        hipLaunchKernelGGL(k_sel_pick, dim3(1), dim3(256), 0, s->stream, st,
+                           pass, want);
+    }
+    hipLaunchKernelGGL(k_sel_count, dim3((unsigned)chunks), dim3(256), 0,
+                       s->stream, keys, valid, n, st, cnt_gt, cnt_eq);
+    hipLaunchKernelGGL(k_sel_scan, dim3(1), dim3(1024), 0, s->stream, st,
+                       cnt_gt, cnt_eq, (uint32_t)chunks);
+    hipLaunchKernelGGL(k_sel_emit, dim3((unsigned)chunks), dim3(256), 0,
+                       s->stream, keys, valid, n, st, cnt_gt, cnt_eq, out,
+                       want);
+    HIP_TRY(s, hipGetLastError());
+    return BYDB_OK;
+}
+
+static int launch_top(bydb_session *s, int64_t min_ts, int64_t max_ts,
+                      PredBlock *preds, int n_preds) {
+    if (s->consumed) {
+        s->err = "top session: one consume per epoch (finalize or reset first)";
+        return BYDB_ERR_STATE;
+    }
+    int flags = KF_NEED_VALUES;
+    if (s->field_vtype == BYDB_VT_FLOAT64) {
+        if (s->float_exp == BYDB_FLOAT_RAW_EXP) {
+            s->err = "top session: raw-float exponent is not supported";
+            return BYDB_ERR_BAD_ARG;
+        }
+        flags |= KF_FLOAT | ((int)(uint16_t)s->float_exp << 16);
+    }
+    s->consumed = true;
+    if (s->top_n == 0) return BYDB_OK;   // the reference's no-op
+    const uint32_t N = (uint32_t)s->top_n;
+    const int64_t nb = s->n_blocks;
+    const uint64_t n_rows = (uint64_t)N * TOP_BLOCK_ROWS;
+    int rc;
+    if (s->top_blocks_cap < nb) {
+        if ((rc = top_alloc(s, &s->d_top_bkeys, (uint64_t)nb)) ||
+            (rc = top_alloc(s, &s->d_top_bvalid, (uint64_t)nb)))
+            return rc;
+        s->top_blocks_cap = nb;
+    }
+    if (s->top_grid_cap != (int64_t)N) {
+        s->top_grid_cap = 0;
+        if ((rc = top_alloc(s, &s->d_top_grid, n_rows)) ||
+            (rc = top_alloc(s, &s->d_top_rvalid, n_rows)) ||
+            (rc = top_alloc(s, &s->d_top_chosen, (uint64_t)N)) ||
+            (rc = top_alloc(s, &s->d_top_winners, (uint64_t)N)) ||
+            (rc = top_alloc(s, &s->d_top_range, (uint64_t)N)) ||
+            (rc = top_alloc(s, &s->d_top_recs, (uint64_t)N)))
+            return rc;
+        s->top_grid_cap = (int64_t)N;
+    }
+    const uint64_t most = (uint64_t)nb > n_rows ? (uint64_t)nb : n_rows;
+    const uint64_t chunks = (most + TOP_CHUNK - 1) / TOP_CHUNK;
+    if (s->top_cnt_cap < chunks) {
+        if ((rc = top_alloc(s, &s->d_top_cnt, 2 * chunks))) return rc;
+        s->top_cnt_cap = chunks;
+    }
+    if (!s->d_top_st && (rc = top_alloc(s, &s->d_top_st, 2))) return rc;
+    const uint64_t limit = s->payload_cap + 4096;
+    HIP_TRY(s, hipEventRecord(s->ev_start, s->stream));
+    HIP_TRY(s, hipMemsetAsync(s->d_top_bvalid, 0, (size_t)nb, s->stream));
+    HIP_TRY(s, hipMemsetAsync(s->d_top_rvalid, 0, (size_t)n_rows, s->stream));
+    int64_t wgs = (nb + 3) / 4;                    // one wave per block
+    int grid = (int)(wgs < 8192 ? wgs : 8192);     // grid-stride beyond
+    hipLaunchKernelGGL(k_top_bounds, dim3(grid), dim3(256), 0, s->stream,
+                       s->d_payload, s->d_sidecar, s->d_blocks, nb, min_ts,
+                       max_ts, flags, s->top_asc, preds, n_preds, s->d_pred_bm,
+                       s->d_pred_flags, s->d_top_bkeys, s->d_top_bvalid,
+                       s->d_err);
+    HIP_TRY(s, hipGetLastError());
+    if ((rc = top_select(s, s->d_top_bkeys, s->d_top_bvalid, (uint64_t)nb, N,
+                         &s->d_top_st[0], s->d_top_chosen)))
+        return rc;
+    hipLaunchKernelGGL(k_top_row_range, dim3((N + 3) / 4), dim3(256), 0,
+                       s->stream, s->d_payload, s->d_blocks, nb, min_ts,
+                       max_ts, flags, &s->d_top_st[0], s->d_top_chosen,
+                       s->d_top_range, N, s->d_err);
+    hipLaunchKernelGGL(k_top_row_keys, dim3(N), dim3(WAVE), 0, s->stream,
+                       s->d_payload, s->d_sidecar, limit, s->d_blocks, nb,
+                       flags, s->top_asc, preds, n_preds, s->d_pred_bm,
+                       s->d_pred_flags, &s->d_top_st[0], s->d_top_chosen,
+                       s->d_top_range, s->d_top_grid, s->d_top_rvalid,
+                       s->d_err);
+    HIP_TRY(s, hipGetLastError());
+    if ((rc = top_select(s, s->d_top_grid, s->d_top_rvalid, n_rows, N,
+                         &s->d_top_st[1], s->d_top_winners)))
+        return rc;
+    hipLaunchKernelGGL(k_top_resolve_keys, dim3((N + 255) / 256), dim3(256), 0,
+                       s->stream, s->d_blocks, nb, flags, s->top_asc,
+                       &s->d_top_st[1], s->d_top_chosen, s->d_top_winners,
+                       s->d_top_grid, s->d_top_recs, N);
+    hipLaunchKernelGGL(k_top_resolve, dim3(N), dim3(WAVE), 0, s->stream,
+                       s->d_payload, limit, s->d_blocks, nb, &s->d_top_st[1],
+                       s->d_top_grid, s->d_top_recs, s->d_err);
+    HIP_TRY(s, hipGetLastError());
+    HIP_TRY(s, hipEventRecord(s->ev_stop, s->stream));
+    return BYDB_OK;
+}
+
+// a top session branches to its own pipeline here, and nowhere else
+static int scan_or_top(bydb_session *s, int64_t min_ts, int64_t max_ts,
+                       PredBlock *preds, int n_preds) {
+    return s->top_on ? launch_top(s, min_ts, max_ts, preds, n_preds)
+                     : launch_scan(s, min_ts, max_ts, preds, n_preds);
+}
+
 // The single point where every consume entry point reaches launch_scan.
 // n_slots is what the resolve stage resolved (0: unfiltered).  Without
 // superseded rows this is launch_scan itself — the same instantiations,
@@ -4904,7 +5690,7 @@ static int ensure_pred_bm(bydb_session *s, uint64_t words) {
 // table to rewrite) and the scan runs with at least one predicate slot.
 static int scan_deduped(bydb_session *s, int64_t min_ts, int64_t max_ts,
                         PredBlock *preds, int n_slots) {
-    if (!dedup_active(s)) return launch_scan(s, min_ts, max_ts, preds, n_slots);
+    if (!dedup_active(s)) return scan_or_top(s, min_ts, max_ts, preds, n_slots);
     if (n_slots == 0) {
         int rc = ensure_pred_buffers(s);
         if (rc != BYDB_OK) return rc;
@@ -4924,7 +5710,7 @@ static int scan_deduped(bydb_session *s, int64_t min_ts, int64_t max_ts,
                        s->d_pred_flags, s->d_pred_bm, s->dd_bm_base,
                        s->d_walk_count);
     HIP_TRY(s, hipGetLastError());
-    return launch_scan(s, min_ts, max_ts, s->d_preds,
+    return scan_or_top(s, min_ts, max_ts, s->d_preds,
                        n_slots > 1 ? n_slots : 1);
 }
 
@@ -5512,6 +6298,129 @@ extern "C" int bydb_finalize(bydb_session *s, bydb_result *out,
     if (rc != BYDB_OK) return rc;
     for (int64_t g = 0; g < n_groups; g++)
         partial_to_result(&parts[(size_t)g], s->field_vtype, s->float_exp, &out[(size_t)g]);
+    return BYDB_OK;
+}
+
+// ---- BatchTop over raw rows: configure, finalize, shard merge ----
+
+extern "C" int bydb_top_configure(bydb_session *s, int field_vtype, int64_t n,
+                                  int asc) {
+    if (n < 0 || n > BYDB_TOP_ROWS_MAX) {
+        s->err = "top n outside 0..BYDB_TOP_ROWS_MAX";
+        return BYDB_ERR_BAD_ARG;
+    }
+    if (field_vtype != BYDB_VT_INT64 && field_vtype != BYDB_VT_FLOAT64) {
+        s->err = "top field_vtype must be int64 or float64";
+        return BYDB_ERR_BAD_ARG;
+    }
+    if (field_vtype == BYDB_VT_FLOAT64 && s->float_exp == BYDB_FLOAT_RAW_EXP) {
+        s->err = "top over a raw-float session is not supported";
+        return BYDB_ERR_BAD_ARG;
+    }
+    // the consume entry points and bydb_reset want a configured session:
+    // a one-group, no-function aggregate that no kernel ever touches
+    int rc = bydb_agg_configure(s, field_vtype, 0, 1, BYDB_MODE_ALL);
+    if (rc != BYDB_OK) return rc;
+    s->top_on = true;
+    s->top_n = n;
+    s->top_asc = asc ? 1 : 0;
+    return BYDB_OK;
+}
+
+extern "C" int bydb_top_finalize(bydb_session *s, bydb_top_row *out,
+                                 int64_t cap, int64_t *out_n) {
+    HIP_TRY(s, hipSetDevice(s->device));
+    if (!s->top_on) { s->err = "not a top session"; return BYDB_ERR_STATE; }
+    if (!out_n) { s->err = "null out_n"; return BYDB_ERR_BAD_ARG; }
+    *out_n = 0;
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    if (!s->consumed || s->top_n == 0) {
+        s->consumed = false;
+        return BYDB_OK;
+    }
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, s->ev_start, s->ev_stop) == hipSuccess)
+        s->last_ms = ms;
+    DevErr de;
+    HIP_TRY(s, hipMemcpy(&de, s->d_err, sizeof de, hipMemcpyDeviceToHost));
+    if (de.code != DERR_NONE) {
+        char buf[128];
+        snprintf(buf, sizeof buf, "device decode error %u at block %u%s",
+                 de.code, de.block_lo,
+                 de.code == DERR_TOP_NULL
+                     ? " (top selected a row of a null-bearing block)" : "");
+        s->err = buf;
+        return BYDB_ERR_BAD_DATA;
+    }
+    TopSelState st;
+    HIP_TRY(s, hipMemcpy(&st, &s->d_top_st[1], sizeof st,
+                         hipMemcpyDeviceToHost));
+    const int64_t got = (int64_t)st.n_out;
+    if (got > s->top_n) { s->err = "top selector overran"; return BYDB_ERR; }
+    *out_n = got;
+    if (cap < got || (got > 0 && !out)) {
+        s->err = "top_finalize: out holds fewer rows than selected";
+        return BYDB_ERR_OOM;   // the epoch stays open: call again
+    }
+    std::vector<TopRec> recs((size_t)got);
+    if (got > 0)
+        HIP_TRY(s, hipMemcpy(recs.data(), s->d_top_recs,
+                             sizeof(TopRec) * (size_t)got,
+                             hipMemcpyDeviceToHost));
+    // the device hands winners over in seq order: a stable sort by key
+    // leaves equal values in input order (top.go:66-82, 190-199)
+    std::stable_sort(recs.begin(), recs.end(),
+                     [](const TopRec &a, const TopRec &b) {
+                         return a.key > b.key;
+                     });
+    const bool is_f = s->field_vtype == BYDB_VT_FLOAT64;
+    for (int64_t i = 0; i < got; i++) {
+        const TopRec &r = recs[(size_t)i];
+        bydb_top_row *o = &out[i];
+        o->series_id = r.series_id;
+        o->ts = r.ts;
+        o->version = r.version;
+        o->value_i = r.value;
+        o->value_f = is_f ? restore_f64(r.value, (int16_t)r.exp) : 0.0;
+        o->seq = r.seq;
+    }
+    s->consumed = false;
+    return BYDB_OK;
+}
+
+extern "C" int bydb_top_rows_merge(const bydb_top_row *const *lists,
+                                   const int64_t *lens, int n_lists,
+                                   int field_vtype, int64_t n, int asc,
+                                   bydb_top_row *out, int64_t *out_n) {
+    if (!out_n || n_lists < 0 || n < 0 || (n_lists > 0 && (!lists || !lens)) ||
+        (field_vtype != BYDB_VT_INT64 && field_vtype != BYDB_VT_FLOAT64))
+        return BYDB_ERR_BAD_ARG;
+    struct Ent { const bydb_top_row *r; int list; };
+    std::vector<Ent> all;
+    for (int l = 0; l < n_lists; l++) {
+        if (lens[l] < 0 || (lens[l] > 0 && !lists[l])) return BYDB_ERR_BAD_ARG;
+        for (int64_t i = 0; i < lens[l]; i++) all.push_back({&lists[l][i], l});
+    }
+    const bool is_f = field_vtype == BYDB_VT_FLOAT64;
+    // better value first; equal values: the earlier list, then the smaller
+    // seq.  Shards restore in their own exponents, so float64 rows compare
+    // as the reference compares them: by value_f.
+    std::stable_sort(all.begin(), all.end(), [&](const Ent &a, const Ent &b) {
+        if (is_f) {
+            if (a.r->value_f != b.r->value_f)
+                return asc ? a.r->value_f < b.r->value_f
+                           : a.r->value_f > b.r->value_f;
+        } else if (a.r->value_i != b.r->value_i) {
+            return asc ? a.r->value_i < b.r->value_i
+                       : a.r->value_i > b.r->value_i;
+        }
+        if (a.list != b.list) return a.list < b.list;
+        return a.r->seq < b.r->seq;
+    });
+    const int64_t take = (int64_t)all.size() < n ? (int64_t)all.size() : n;
+    *out_n = take;
+    if (take > 0 && !out) return BYDB_ERR_BAD_ARG;
+    for (int64_t i = 0; i < take; i++) out[i] = *all[(size_t)i].r;
     return BYDB_OK;
 }
 

@@ -671,6 +671,89 @@ int bydb_top_groups(const bydb_result *results, int64_t n_groups,
                     int value_sel, int64_t k, int asc, int64_t *out_idx,
                     int64_t *out_n);
 
+/* ---- top-N data points by field value: raw-row BatchTop ----
+ * A measure query's plan is Scan -> [GroupByAgg] -> [Top] -> Limit
+ * (pkg/query/vectorized/measure/plan/analyzer.go:118-151).  With `top` and
+ * no `agg`, measure.BatchTop runs over every data point the scan yields, in
+ * one global heap (plan/top.go:28-46, top.go:30-199): a whole-result top-N,
+ * "the 10 highest response times in the last hour where env = prod".  This
+ * is that operator on the same seam (BreakerOperator Init / Consume /
+ * Finalize / NextBatch): the session selects rows instead of folding them.
+ *
+ * Order contract (top.go:30-34, 66-82, 190-199): desc keeps the N highest,
+ * highest first; asc the N lowest, lowest first.  Equal values surface in
+ * input order and the earlier row wins a place.  Input order is storage
+ * order, seq = (item << 13) | row — the key bydb_group_first_seen documents
+ * as the reference's row-iteration order.
+ *
+ * Two limits of this version:
+ *  - Null-bearing field blocks (BYDB_ENC_PLAIN cells) rank nulls lowest in
+ *    the reference (top.go:95-105).  Here a top consume that selects any
+ *    row of such a block is a loud device error (bydb_top_finalize returns
+ *    BYDB_ERR_BAD_DATA); a null row is never dropped silently.  A Plain
+ *    block the clamp or the filter leaves no row of is not an error.
+ *    Raw-float sessions (BYDB_FLOAT_RAW_EXP) consist of such blocks and are
+ *    out of scope.
+ *  - float64 keys are compared as decimal mantissas rescaled exactly to the
+ *    session exponent (the rescale the min/max aggregates use; an overflow
+ *    is the same loud device error).  The reference compares restored
+ *    doubles, so two different decimals that round to the same double tie
+ *    there and are ordered by their decimals here.  That needs mantissas
+ *    beyond 2^53. */
+#define BYDB_TOP_ROWS_MAX 1024
+typedef struct {
+    uint64_t series_id;
+    int64_t  ts;
+    int64_t  version;
+    int64_t  value_i;   /* int64 field: the value; float64 field: the row's
+                           decimal mantissa in its own block's exponent */
+    double   value_f;   /* float64 field: restore(value_i, block exp), the
+                           same restore finalize applies (float.go:69-102);
+                           int64 field: 0 */
+    uint64_t seq;       /* (item << 13) | row, storage order */
+} bydb_top_row;         /* 48 bytes */
+
+/* BuildOperators' Top stage (plan/top.go:28-46) in place of
+ * BatchAggregation: makes the session a BatchTop operator over raw rows; a
+ * later bydb_agg_configure* switches it back.  BYDB_ERR_BAD_ARG (session
+ * stays usable, configuration unchanged) when n < 0, n > BYDB_TOP_ROWS_MAX,
+ * field_vtype is not int64 / float64, or the session exponent is
+ * BYDB_FLOAT_RAW_EXP (also checked by the consume).  n == 0 is legal and
+ * the reference's no-op (top.go:152-157): consume launches nothing,
+ * finalize returns 0 rows.  For float64 fields the session exponent
+ * (bydb_set_float_exp) means what it means for aggregates: the part's
+ * minimum exponent, the domain every key is compared in.
+ *
+ * Every consume entry point (bydb_consume, _multi, _filter, _filter_tree,
+ * with or without bydb_set_row_dedup) then selects under exactly the
+ * aggregate path's rules: clamp, skip verdicts, code-mask and bitmap
+ * walkers, dedup survivors removed before the filter (BatchTop.Consume,
+ * top.go:152-188).  One consume per epoch: a second one before
+ * bydb_top_finalize or bydb_reset is BYDB_ERR_STATE.  bydb_last_consume_ms
+ * reports the event-timed span of all top kernels. */
+int bydb_top_configure(bydb_session *s, int field_vtype, int64_t n, int asc);
+
+/* BatchTop.Finalize / NextBatch (top.go:190-199): syncs, then writes
+ * min(n, selected rows) rows sorted by (value, then seq ascending) and
+ * their count to *out_n, and closes the epoch.  BYDB_ERR_OOM when cap is
+ * smaller than that count: *out_n holds the needed count and the epoch
+ * stays open.  BYDB_ERR_STATE when the session is not a top session,
+ * BYDB_ERR_BAD_DATA on a device error (sticky until bydb_reset). */
+int bydb_top_finalize(bydb_session *s, bydb_top_row *out, int64_t cap,
+                      int64_t *out_n);
+
+/* Pure host, no GPU, no session: the reduce side for time-bucket shards
+ * (ApplyTopToReduce, reduce.go:290, over raw rows) — a stable N-way merge
+ * of per-shard bydb_top_finalize results.  On equal values the earlier
+ * list wins, then the smaller seq.  int64 rows compare by value_i; float64
+ * rows by value_f, as the reference does (shards restore in their own
+ * exponents).  out holds min(n, total rows) rows and must not alias a
+ * list.  BYDB_ERR_BAD_ARG on null outputs, negative counts or an unknown
+ * field_vtype. */
+int bydb_top_rows_merge(const bydb_top_row *const *lists, const int64_t *lens,
+                        int n_lists, int field_vtype, int64_t n, int asc,
+                        bydb_top_row *out, int64_t *out_n);
+
 /* ---- AggModeReduce over raw map frames, with replica dedup ----
  * Restates the liaison reduce (aggregation_reduce.go:83-138 +
  * ReduceRawFrames, reduce.go:78): rows keyed by the key columns
