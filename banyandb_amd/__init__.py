@@ -84,6 +84,7 @@ OP_IN, OP_NOT_IN = 9, 10
 TAG_STRING, TAG_INT = 1, 2
 FILTER_MAX_CONDS = 8
 TOP_ROWS_MAX = 1024
+ORDER_TS_ASC, ORDER_TS_DESC = 0, 1
 
 
 class TopRow(C.Structure):
@@ -399,6 +400,17 @@ def _load():
                                         C.POINTER(C.c_int64), C.c_int, C.c_int,
                                         C.c_int64, C.c_int, C.POINTER(TopRow),
                                         C.POINTER(C.c_int64)]
+    lib.bydb_rows_configure.restype = C.c_int
+    lib.bydb_rows_configure.argtypes = [C.c_void_p, C.c_int, C.c_int64,
+                                        C.c_int64, C.c_int]
+    lib.bydb_rows_finalize.restype = C.c_int
+    lib.bydb_rows_finalize.argtypes = [C.c_void_p, C.POINTER(TopRow),
+                                       C.c_int64, C.POINTER(C.c_int64)]
+    lib.bydb_rows_merge.restype = C.c_int
+    lib.bydb_rows_merge.argtypes = [C.POINTER(C.POINTER(TopRow)),
+                                    C.POINTER(C.c_int64), C.c_int, C.c_int64,
+                                    C.c_int64, C.c_int, C.POINTER(TopRow),
+                                    C.POINTER(C.c_int64)]
     lib.bydb_reduce_partials2.restype = C.c_int
     lib.bydb_reduce_partials2.argtypes = [C.POINTER(Partial), C.c_int64, C.c_int64,
                                           C.c_int, C.c_int16, C.POINTER(Result)]
@@ -731,6 +743,29 @@ class Session:
         self._ck(_lib.bydb_top_finalize(self._h, out, cap, C.byref(got)))
         return [out[i] for i in range(got.value)]
 
+    def configure_rows(self, field_vtype, offset, limit, desc=False,
+                       float_exp=0):
+        """Make the session a Scan -> Limit operator (query.go:913-1026,
+        limit.go:81-108): the next consume selects rows [offset, offset +
+        limit) of the rows it would have aggregated, ordered by (timestamp,
+        descending when `desc`; series_id ascending; storage order);
+        scan_rows() returns them.  configure*() switches back."""
+        self._ck(_lib.bydb_set_float_exp(self._h, float_exp))
+        self._ck(_lib.bydb_rows_configure(
+            self._h, field_vtype, offset, limit,
+            ORDER_TS_DESC if desc else ORDER_TS_ASC))
+        self.n_groups = 1
+        self.field_vtype = field_vtype
+        self.rows_limit = limit
+
+    def scan_rows(self):
+        """Finalize a row-scan epoch: at most `limit` TopRow, in order."""
+        cap = max(int(self.rows_limit), 1)
+        out = (TopRow * cap)()
+        got = C.c_int64(0)
+        self._ck(_lib.bydb_rows_finalize(self._h, out, cap, C.byref(got)))
+        return [out[i] for i in range(got.value)]
+
     def set_partials_buffer(self, dev_ptr, nbytes):
         self._ck(_lib.bydb_set_partials_buffer(self._h, dev_ptr, nbytes))
 
@@ -870,6 +905,25 @@ def top_rows_merge(lists, field_vtype, n, asc=False):
                                   1 if asc else 0, out, C.byref(got))
     if rc != 0:
         raise RuntimeError(f"top_rows_merge rc={rc}")
+    return [out[i] for i in range(got.value)]
+
+
+def rows_merge(lists, offset, limit, desc=False):
+    """Host reduce side of a sharded row scan: per-shard scan_rows() results
+    (each configured with offset 0 and limit offset + limit) merged by
+    (timestamp, series_id), the earlier list first on a full tie, then cut
+    to [offset, offset + limit)."""
+    arrs = [(TopRow * max(len(l), 1))(*l) for l in lists]
+    ptrs = (C.POINTER(TopRow) * max(len(lists), 1))(
+        *[C.cast(a, C.POINTER(TopRow)) for a in arrs])
+    lens = (C.c_int64 * max(len(lists), 1))(*[len(l) for l in lists])
+    out = (TopRow * max(limit, 1))()
+    got = C.c_int64(0)
+    rc = _lib.bydb_rows_merge(ptrs, lens, len(lists), offset, limit,
+                              ORDER_TS_DESC if desc else ORDER_TS_ASC, out,
+                              C.byref(got))
+    if rc != 0:
+        raise RuntimeError(f"rows_merge rc={rc}")
     return [out[i] for i in range(got.value)]
 
 

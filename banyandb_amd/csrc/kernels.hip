@@ -4420,6 +4420,414 @@ __global__ __launch_bounds__(WAVE) void k_top_resolve(
     }
 }
 
+// ---------------- Scan -> Limit over raw rows ----------------
+// A measure query with neither `agg` nor `top` is Scan -> Limit
+// (pkg/query/vectorized/measure/plan/analyzer.go:118-157): queryResult's
+// heap merges the block cursors of all parts by timestamp, equal timestamps
+// by seriesID ascending (banyand/measure/query.go:913-943, 962-1026;
+// SORT_DESC walks the cursors backwards, :286-296), and BatchLimit keeps
+// rows [offset, offset + limit) of that stream (limit.go:81-108).
+//
+// The order is total on selected rows: (ts in the requested direction,
+// series_id ascending and unsigned, seq ascending).  N = offset + limit.
+// The containment argument of the top-N section holds for any total order:
+// key each block by its best selected row — the first one ascending, the
+// last one descending, timestamps never fall inside a block — and order
+// blocks by (key, index).  Were a row r of block B outside the N best
+// blocks, N other blocks would each hold a row before r: a better
+// (ts, series), or the same pair in a smaller block index and so a smaller
+// seq.  So again two exact selections, N blocks and then N rows of their
+// grid, but under a two-word key: hi = the timestamp key (top_key, larger
+// is better in both directions), lo = ~series_id.
+//
+// The block-key pass opens no field stream, and no timestamp stream for a
+// block the clamp covers whole and no walker filters: "latest N" over such
+// a part is a sweep of the descriptors.
+#define ROWS_DEFER 2   // validity byte: hi holds a row index, not yet a key
+
+// Stage 1 — one wave per block, grid-stride: the two-word key of the
+// block's best selected row.  Const / DeltaConst timestamps and the rows
+// the descriptor knows (row 0, row count - 1) are closed form; any other
+// row of a stream-coded list is left to k_rows_bounds_ts.
+// (launch bounds: see top_clamp)
+__global__ __launch_bounds__(256, 4) void k_rows_bounds(
+    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
+    uint64_t limit, const bydb_block_desc *__restrict__ blocks,
+    int64_t n_blocks, int64_t min_ts, int64_t max_ts, int flags, int desc,
+    const PredBlock *__restrict__ preds, int n_preds,
+    const uint64_t *__restrict__ pred_bm,
+    const uint8_t *__restrict__ pred_flags, uint64_t *__restrict__ hi,
+    uint64_t *__restrict__ lo, uint8_t *__restrict__ valid, DevErr *derr) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave_id =
+        (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t bi = wave_id; bi < n_blocks; bi += n_waves) {
+        const bydb_block_desc *bd = &blocks[bi];
+        TopSel ts;
+        if (!top_clamp(payload, bd, bi, min_ts, max_ts, flags, lane, derr,
+                       &ts) ||
+            !top_walkers(payload, sidecar, bi, n_blocks, preds, n_preds,
+                         pred_bm, pred_flags, derr, &ts))
+            continue;
+        if (bd->field_enc == BYDB_ENC_PLAIN) {
+            // null-bearing block: never return a null row as a value
+            if (top_any_row(&ts, lane))
+                dev_set_err(derr, DERR_TOP_NULL, (uint64_t)bi);
+            continue;
+        }
+        int64_t row = -1;
+        if (!ts.wp[0] && !ts.wp[1] && !ts.wp[2]) {
+            row = desc ? ts.r1 : ts.r0;
+        } else {
+            // RLE walkers are forward cursors: descending keeps the last
+            // match of the whole range, ascending stops at the first
+            for (int64_t base = ts.r0; base <= ts.r1; base += WAVE) {
+                const int64_t r = base + lane;
+                const bool need = r <= ts.r1;
+                const bool ok =
+                    walkers_match(ts.wp[0], ts.wp[1], ts.wp[2], r, need) &&
+                    need;
+                const uint64_t m = __ballot(ok);
+                if (!m) continue;
+                if (desc) {
+                    row = base + 63 - __clzll(m);
+                } else {
+                    row = base + __ffsll((unsigned long long)m) - 1;
+                    break;
+                }
+            }
+        }
+        if (row < 0) continue;
+        const int64_t n = (int64_t)bd->count;
+        const uint8_t tenc = bd->ts_enc_with_version;
+        const uint8_t tc = tenc >= BYDB_ENC_CONST_WV ? tenc - 4 : tenc;
+        int64_t t = bd->ts_min;
+        bool defer = false;
+        if (row == 0 || tc == BYDB_ENC_CONST) {
+            // ts_min
+        } else if (row == n - 1) {
+            t = bd->ts_max;
+        } else if (tc == BYDB_ENC_DELTA_CONST) {
+            if (bd->ts_off + 11 > limit) {
+                dev_set_err(derr, DERR_BAD_STREAM, (uint64_t)bi);
+                continue;
+            }
+            int vl;
+            const int64_t dd = decode_one_varint(payload + bd->ts_off, &vl);
+            t = (int64_t)((uint64_t)bd->ts_min + (uint64_t)row * (uint64_t)dd);
+        } else if (tc == BYDB_ENC_DELTA || tc == BYDB_ENC_DELTA_OF_DELTA) {
+            defer = true;
+        } else {
+            dev_set_err(derr, DERR_BAD_ENC, (uint64_t)bi);
+            continue;
+        }
+        if (lane == 0) {
+            lo[bi] = ~bd->series_id;
+            hi[bi] = defer ? (uint64_t)row : top_key(t, desc == 0);
+            valid[bi] = defer ? ROWS_DEFER : 1;
+        }
+    }
+}
+
+// Stage 1b — the deferred keys: one wave per workgroup, grid-stride, each
+// workgroup decoding into its own slot of the (still free) row grid, as
+// k_top_resolve does.  A 64-thread kernel for the decoder it calls.
+__global__ __launch_bounds__(WAVE) void k_rows_bounds_ts(
+    const uint8_t *__restrict__ payload, uint64_t limit,
+    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks, int desc,
+    uint64_t *__restrict__ hi, uint8_t *__restrict__ valid,
+    uint64_t *__restrict__ grid, DevErr *derr) {
+    const int lane = threadIdx.x;
+    int64_t *scratch = (int64_t *)(grid + (uint64_t)blockIdx.x * TOP_BLOCK_ROWS);
+    // 64 validity bytes per step, one per lane; the deferred ones in turn
+    for (int64_t base = (int64_t)blockIdx.x * WAVE; base < n_blocks;
+         base += (int64_t)gridDim.x * WAVE) {
+        uint64_t todo = __ballot(base + lane < n_blocks &&
+                                 valid[base + lane] == ROWS_DEFER);
+        for (; todo; todo &= todo - 1) {
+            const int64_t bi = base + __ffsll((unsigned long long)todo) - 1;
+            const bydb_block_desc *bd = &blocks[bi];
+            const int64_t n = (int64_t)bd->count;
+            const uint64_t row = hi[bi];
+            if (n < 1 || n > TOP_BLOCK_ROWS || row >= (uint64_t)n) {
+                dev_set_err(derr, DERR_BAD_ENC, (uint64_t)bi);
+                if (lane == 0) valid[bi] = 0;
+                continue;
+            }
+            const uint8_t tenc = bd->ts_enc_with_version;
+            const uint8_t tc = tenc >= BYDB_ENC_CONST_WV ? tenc - 4 : tenc;
+            dedup_decode_list(payload, bd->ts_off, limit, tc, bd->ts_min, n,
+                              true, lane, scratch, derr, (uint64_t)bi);
+            __threadfence();
+            const int64_t t = scratch[row];
+            __threadfence();   // read before the next block reuses the slot
+            if (lane == 0) {
+                hi[bi] = top_key(t, desc == 0);
+                valid[bi] = 1;
+            }
+        }
+    }
+}
+
+// ---- rows_select: top_select under a two-word key ----
+// Best = hi descending, then lo descending, then index ascending.  The hi
+// word goes through k_sel_hist / k_sel_pick unchanged: they leave the
+// threshold T and the rank still open among entries with hi == T.  The
+// same eight passes then run over lo for those entries only, and the stable
+// count / scan / emit takes hi > T, or hi == T and lo above its threshold,
+// or both equal in index order while the rank lasts.  lo is indexed through
+// lo_map when given: entry i's word is lo[lo_map[i >> 13]] (a row's lo is
+// its block's).
+__device__ __forceinline__ uint64_t sel2_lo(const uint64_t *lo,
+                                            const uint32_t *lo_map,
+                                            uint64_t i) {
+    return lo_map ? lo[lo_map[i >> 13]] : lo[i];
+}
+
+__global__ __launch_bounds__(256) void k_sel2_hist(
+    const uint64_t *__restrict__ hi, const uint64_t *__restrict__ lo,
+    const uint32_t *__restrict__ lo_map, const uint8_t *__restrict__ valid,
+    uint64_t n, const TopSelState *st_hi, TopSelState *st, int pass) {
+    __shared__ uint32_t h[256];
+    if (st_hi->all) return;
+    const uint64_t thr = st_hi->prefix;
+    const uint64_t prefix = pass == 0 ? 0ull : st->prefix;
+    const uint64_t mask = pass == 0 ? 0ull : ~0ull << (64 - 8 * pass);
+    const int shift = 56 - 8 * pass;
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n;
+         i += (uint64_t)gridDim.x * 256) {
+        if (!valid[i] || hi[i] != thr) continue;
+        const uint64_t k = sel2_lo(lo, lo_map, i);
+        if ((k & mask) == prefix) atomicAdd(&h[(k >> shift) & 255], 1u);
+    }
+    __syncthreads();
+    if (h[threadIdx.x]) atomicAdd(&st->hist[threadIdx.x], h[threadIdx.x]);
+}
+
+// One workgroup of 256.  Pass 0 takes over the rank the hi passes left.
+// Invariant: the entries with hi == T that match the prefix number at least
+// `remaining`.
+__global__ __launch_bounds__(256) void k_sel2_pick(const TopSelState *st_hi,
+                                                   TopSelState *st, int pass) {
+    __shared__ uint32_t h[256];
+    h[threadIdx.x] = st->hist[threadIdx.x];
+    st->hist[threadIdx.x] = 0;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    if (pass == 0) {
+        st->prefix = 0;
+        st->remaining = st_hi->remaining;
+        st->all = st_hi->all;
+        st->n_out = 0;
+    }
+    if (st->all) return;
+    uint32_t rem = st->remaining, cum = 0;
+    int digit = 0;
+    for (int b = 255; b >= 0; b--) {
+        if (cum + h[b] >= rem) { digit = b; break; }
+        cum += h[b];
+    }
+    st->prefix |= (uint64_t)digit << (56 - 8 * pass);
+    st->remaining = rem - cum;
+}
+
+// sel_class under the two-word key
+__device__ __forceinline__ uint32_t sel2_class(
+    const uint64_t *hi, const uint64_t *lo, const uint32_t *lo_map,
+    const uint8_t *valid, uint64_t i, uint64_t n, uint64_t thr_hi,
+    uint64_t thr_lo, bool all) {
+    if (i >= n || !valid[i]) return 0;
+    if (all) return 2;
+    const uint64_t h = hi[i];
+    if (h != thr_hi) return h > thr_hi ? 2 : 0;
+    const uint64_t l = sel2_lo(lo, lo_map, i);
+    return l > thr_lo ? 2 : l == thr_lo ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void k_sel2_count(
+    const uint64_t *__restrict__ hi, const uint64_t *__restrict__ lo,
+    const uint32_t *__restrict__ lo_map, const uint8_t *__restrict__ valid,
+    uint64_t n, const TopSelState *st_hi, const TopSelState *st,
+    uint32_t *__restrict__ cnt_gt, uint32_t *__restrict__ cnt_eq) {
+    __shared__ uint32_t s_gt, s_eq;
+    if (threadIdx.x == 0) { s_gt = 0; s_eq = 0; }
+    __syncthreads();
+    const uint64_t thr_hi = st_hi->prefix, thr_lo = st->prefix;
+    const bool all = st->all != 0;
+    const uint64_t i0 = (uint64_t)blockIdx.x * TOP_CHUNK + threadIdx.x * 4;
+    uint32_t g = 0, e = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        uint32_t c = sel2_class(hi, lo, lo_map, valid, i0 + k, n, thr_hi,
+                                thr_lo, all);
+        g += c == 2;
+        e += c == 1;
+    }
+    if (g) atomicAdd(&s_gt, g);
+    if (e) atomicAdd(&s_eq, e);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        cnt_gt[blockIdx.x] = s_gt;
+        cnt_eq[blockIdx.x] = s_eq;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_sel2_emit(
+    const uint64_t *__restrict__ hi, const uint64_t *__restrict__ lo,
+    const uint32_t *__restrict__ lo_map, const uint8_t *__restrict__ valid,
+    uint64_t n, const TopSelState *st_hi, const TopSelState *st,
+    const uint32_t *__restrict__ sel_before,
+    const uint32_t *__restrict__ eq_before, uint32_t *__restrict__ out,
+    uint32_t out_cap) {
+    __shared__ uint32_t w4[4];
+    const uint64_t thr_hi = st_hi->prefix, thr_lo = st->prefix;
+    const bool all = st->all != 0;
+    const uint32_t rem = all ? 0 : st->remaining;
+    const uint64_t i0 = (uint64_t)blockIdx.x * TOP_CHUNK + threadIdx.x * 4;
+    uint32_t cls[4], e = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        cls[k] = sel2_class(hi, lo, lo_map, valid, i0 + k, n, thr_hi, thr_lo,
+                            all);
+        e += cls[k] == 1;
+    }
+    uint32_t eq_rank = eq_before[blockIdx.x] + sel_block_scan(e, w4);
+    uint32_t s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (cls[k] == 1) cls[k] = eq_rank++ < rem ? 2 : 0;
+        s += cls[k] == 2;
+    }
+    uint32_t at = sel_before[blockIdx.x] + sel_block_scan(s, w4);
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (cls[k] == 2) {
+            if (at < out_cap) out[at] = (uint32_t)(i0 + k);
+            at++;
+        }
+}
+
+// Stage 3 — one wave per chosen block (ascending block index, so grid
+// index order is seq order): the timestamp list decoded into the block's
+// slot of the row grid, then every selected row's timestamp replaced by its
+// key.  [r0, r1] comes from k_top_row_range; rvalid is pre-zeroed.
+__global__ __launch_bounds__(WAVE) void k_rows_row_keys(
+    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
+    uint64_t limit, const bydb_block_desc *__restrict__ blocks,
+    int64_t n_blocks, int desc, const PredBlock *__restrict__ preds,
+    int n_preds, const uint64_t *__restrict__ pred_bm,
+    const uint8_t *__restrict__ pred_flags, const TopSelState *st,
+    const uint32_t *__restrict__ chosen, const uint32_t *__restrict__ range,
+    uint64_t *__restrict__ grid, uint8_t *__restrict__ rvalid, DevErr *derr) {
+    const int lane = threadIdx.x;
+    const uint32_t c = blockIdx.x;
+    if (c >= st->n_out) return;
+    const int64_t bi = (int64_t)chosen[c];
+    if (bi >= n_blocks || range[c] == TOP_NO_ROWS) return;
+    const bydb_block_desc *bd = &blocks[bi];
+    TopSel ts;
+    ts.r0 = (int64_t)(range[c] & 0xFFFFu);
+    ts.r1 = (int64_t)(range[c] >> 16);
+    ts.fdiff = 0;
+    if (!top_walkers(payload, sidecar, bi, n_blocks, preds, n_preds, pred_bm,
+                     pred_flags, derr, &ts))
+        return;
+    const int64_t n = (int64_t)bd->count;
+    int64_t *tsv = (int64_t *)(grid + (uint64_t)c * TOP_BLOCK_ROWS);
+    uint8_t *ok_out = rvalid + (uint64_t)c * TOP_BLOCK_ROWS;
+    const uint8_t tenc = bd->ts_enc_with_version;
+    const uint8_t tc = tenc >= BYDB_ENC_CONST_WV ? tenc - 4 : tenc;
+    if (tc == BYDB_ENC_CONST) {
+        for (int64_t i = lane; i < n; i += WAVE) tsv[i] = bd->ts_min;
+    } else if (tc == BYDB_ENC_DELTA_CONST || tc == BYDB_ENC_DELTA ||
+               tc == BYDB_ENC_DELTA_OF_DELTA) {
+        dedup_decode_list(payload, bd->ts_off, limit, tc, bd->ts_min, n, true,
+                          lane, tsv, derr, (uint64_t)bi);
+    } else {
+        dev_set_err(derr, DERR_BAD_ENC, (uint64_t)bi);
+        return;
+    }
+    // the decode stores a row from whichever lane held its terminator
+    __threadfence();
+    for (int64_t base = ts.r0; base <= ts.r1; base += WAVE) {
+        const int64_t row = base + lane;
+        const bool need = row <= ts.r1;
+        const bool ok =
+            walkers_match(ts.wp[0], ts.wp[1], ts.wp[2], row, need) && need;
+        if (ok) {
+            tsv[row] = (int64_t)top_key(tsv[row], desc == 0);
+            ok_out[row] = 1;
+        }
+    }
+}
+
+// Stage 5a — one thread per winner: series, seq and exponent from the grid
+// index and the descriptor.  It runs before k_top_resolve (timestamp and
+// version) and 5b, which reuse the grid as decode scratch.
+__global__ __launch_bounds__(256) void k_rows_resolve_keys(
+    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
+    const TopSelState *st_rows, const uint32_t *__restrict__ chosen,
+    const uint32_t *__restrict__ winners, const uint64_t *__restrict__ grid,
+    TopRec *__restrict__ recs, uint32_t cap) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= st_rows->n_out || i >= cap) return;
+    const uint32_t idx = winners[i];
+    const uint32_t row = idx & (TOP_BLOCK_ROWS - 1);
+    const int64_t bi = (idx >> 13) < cap ? (int64_t)chosen[idx >> 13] : n_blocks;
+    TopRec r = {};
+    r.seq = ~0ull;   // no block: the later stages leave the record alone
+    if (bi < n_blocks) {
+        const bydb_block_desc *bd = &blocks[bi];
+        r.series_id = bd->series_id;
+        r.key = grid[idx];
+        r.seq = ((uint64_t)bi << 13) | row;
+        r.exp = bd->exp;
+    }
+    recs[i] = r;
+}
+
+// Stage 5b — one wave per winner, after k_top_resolve: the field value, in
+// the winner's own block exponent, from a decode of the winner's field
+// column into its slot of the grid (as k_top_row_keys decodes it).
+__global__ __launch_bounds__(WAVE) void k_rows_resolve_field(
+    const uint8_t *__restrict__ payload, uint64_t limit,
+    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
+    const TopSelState *st_rows, uint64_t *__restrict__ grid,
+    TopRec *__restrict__ recs, DevErr *derr) {
+    const int lane = threadIdx.x;
+    const uint32_t i = blockIdx.x;
+    if (i >= st_rows->n_out) return;
+    const uint64_t seq = recs[i].seq;
+    const int64_t bi = (int64_t)(seq >> 13);
+    const int64_t row = (int64_t)(seq & (TOP_BLOCK_ROWS - 1));
+    if (bi >= n_blocks) return;
+    const bydb_block_desc *bd = &blocks[bi];
+    const int64_t n = (int64_t)bd->count;
+    if (n < 1 || n > TOP_BLOCK_ROWS || row >= n) return;
+    int64_t *scratch = (int64_t *)(grid + (uint64_t)i * TOP_BLOCK_ROWS);
+    const uint8_t fenc = bd->field_enc;
+    int64_t v = bd->field_first;
+    if (fenc == BYDB_ENC_DELTA_CONST || fenc == BYDB_ENC_DELTA ||
+        fenc == BYDB_ENC_DELTA_OF_DELTA) {
+        if (bd->field_off & TAG_SIDECAR_BIT) {
+            dev_set_err(derr, DERR_BAD_ENC, (uint64_t)bi);
+            return;
+        }
+        dedup_decode_list(payload, bd->field_off, limit, fenc, bd->field_first,
+                          n, false, lane, scratch, derr, (uint64_t)bi);
+        __threadfence();
+        v = scratch[row];
+    } else if (fenc != BYDB_ENC_CONST) {
+        // a Plain block never carries a valid key
+        dev_set_err(derr, DERR_BAD_ENC, (uint64_t)bi);
+        return;
+    }
+    if (lane == 0) recs[i].value = v;
+}
+
 // ===================== host session =====================
 
 struct bydb_session {
@@ -4531,6 +4939,16 @@ struct bydb_session {
     uint32_t *d_top_cnt = nullptr;      // selector chunk counters, 2 arrays
     uint64_t top_cnt_cap = 0;           // chunks per array
     TopSelState *d_top_st = nullptr;    // [2]: block select, row select
+    // Scan -> Limit over raw rows (bydb_rows_configure): the session returns
+    // rows [offset, offset + limit) of the time-ordered selection.  It
+    // shares the top session's scratch; its own are the second key word per
+    // block and the selector states of the two-word selects.
+    bool rows_on = false;
+    int64_t rows_offset = 0, rows_limit = 0;
+    int rows_desc = 0;
+    uint64_t *d_rows_blo = nullptr;     // [n_blocks] ~series_id
+    int64_t rows_blocks_cap = 0;
+    TopSelState *d_rows_st = nullptr;   // [4]: blocks hi, lo; rows hi, lo
 };
 
 // What a read-once pass has to exceed before its loads bypass the caches:
@@ -4591,7 +5009,7 @@ static void top_free(bydb_session *s) {
     void *ptrs[] = {s->d_top_bkeys, s->d_top_bvalid, s->d_top_grid,
                     s->d_top_rvalid, s->d_top_chosen, s->d_top_winners,
                     s->d_top_recs, s->d_top_cnt, s->d_top_st,
-                    s->d_top_range};
+                    s->d_top_range, s->d_rows_blo, s->d_rows_st};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     s->d_top_bkeys = nullptr; s->d_top_bvalid = nullptr;
@@ -4599,6 +5017,8 @@ static void top_free(bydb_session *s) {
     s->d_top_chosen = nullptr; s->d_top_winners = nullptr;
     s->d_top_recs = nullptr; s->d_top_cnt = nullptr; s->d_top_st = nullptr;
     s->d_top_range = nullptr;
+    s->d_rows_blo = nullptr; s->d_rows_st = nullptr;
+    s->rows_blocks_cap = 0;
     s->top_blocks_cap = 0; s->top_grid_cap = 0; s->top_cnt_cap = 0;
 }
 
@@ -4841,6 +5261,7 @@ extern "C" int bydb_agg_configure(bydb_session *s, int field_vtype,
     HIP_TRY(s, hipSetDevice(s->device));
     if (n_groups < 1) { s->err = "n_groups < 1"; return BYDB_ERR_BAD_ARG; }
     s->top_on = false;   // a BatchAggregation operator again
+    s->rows_on = false;
     s->field_vtype = field_vtype;
     s->func_mask = func_mask;
     s->n_groups = n_groups;
@@ -5675,11 +6096,158 @@ static int launch_top(bydb_session *s, int64_t min_ts, int64_t max_ts,
     return BYDB_OK;
 }
 
-// a top session branches to its own pipeline here, and nowhere else
+// ---- Scan -> Limit over raw rows: the pipeline of one consume ----
+// (header: "time-ordered rows with offset and limit"; kernels:
+// k_rows_bounds*, k_sel2_*, k_rows_row_keys, k_rows_resolve*)
+
+// rows_select(hi, lo, valid, n, want) -> out[], count in st->n_out.
+static int rows_select(bydb_session *s, const uint64_t *hi, const uint64_t *lo,
+                       const uint32_t *lo_map, const uint8_t *valid,
+                       uint64_t n, uint32_t want, TopSelState *st_hi,
+                       TopSelState *st, uint32_t *out) {
+    const uint64_t chunks = (n + TOP_CHUNK - 1) / TOP_CHUNK;
+    uint32_t *cnt_gt = s->d_top_cnt, *cnt_eq = s->d_top_cnt + s->top_cnt_cap;
+    const int hgrid = (int)(chunks < 2048 ? chunks : 2048);
+    HIP_TRY(s, hipMemsetAsync(st_hi, 0, sizeof(TopSelState), s->stream));
+    HIP_TRY(s, hipMemsetAsync(st, 0, sizeof(TopSelState), s->stream));
+    for (int pass = 0; pass < 8; pass++) {
+        hipLaunchKernelGGL(k_sel_hist, dim3(hgrid), dim3(256), 0, s->stream,
+                           hi, valid, n, st_hi, pass);
+        hipLaunchKernelGGL(k_sel_pick, dim3(1), dim3(256), 0, s->stream, st_hi,
+                           pass, want);
+    }
+    for (int pass = 0; pass < 8; pass++) {
+        hipLaunchKernelGGL(k_sel2_hist, dim3(hgrid), dim3(256), 0, s->stream,
+                           hi, lo, lo_map, valid, n, st_hi, st, pass);
+        hipLaunchKernelGGL(k_sel2_pick, dim3(1), dim3(256), 0, s->stream,
+                           st_hi, st, pass);
+    }
+    hipLaunchKernelGGL(k_sel2_count, dim3((unsigned)chunks), dim3(256), 0,
+                       s->stream, hi, lo, lo_map, valid, n, st_hi, st, cnt_gt,
+                       cnt_eq);
+    hipLaunchKernelGGL(k_sel_scan, dim3(1), dim3(1024), 0, s->stream, st,
+                       cnt_gt, cnt_eq, (uint32_t)chunks);
+    hipLaunchKernelGGL(k_sel2_emit, dim3((unsigned)chunks), dim3(256), 0,
+                       s->stream, hi, lo, lo_map, valid, n, st_hi, st, cnt_gt,
+                       cnt_eq, out, want);
+    HIP_TRY(s, hipGetLastError());
+    return BYDB_OK;
+}
+
+// the fewest grid slots a row scan keeps: k_rows_bounds_ts decodes one
+// deferred block per slot at a time, whatever N is
+#define ROWS_MIN_SLOTS 256
+
+static int launch_rows(bydb_session *s, int64_t min_ts, int64_t max_ts,
+                       PredBlock *preds, int n_preds) {
+    if (s->consumed) {
+        s->err = "row scan: one consume per epoch (finalize or reset first)";
+        return BYDB_ERR_STATE;
+    }
+    int flags = KF_NEED_VALUES;
+    if (s->field_vtype == BYDB_VT_FLOAT64) {
+        if (s->float_exp == BYDB_FLOAT_RAW_EXP) {
+            s->err = "row scan: raw-float exponent is not supported";
+            return BYDB_ERR_BAD_ARG;
+        }
+        flags |= KF_FLOAT | ((int)(uint16_t)s->float_exp << 16);
+    }
+    s->consumed = true;
+    if (s->rows_limit == 0) return BYDB_OK;   // BatchLimit with nothing to keep
+    const uint32_t N = (uint32_t)(s->rows_offset + s->rows_limit);
+    const uint32_t slots = N < ROWS_MIN_SLOTS ? ROWS_MIN_SLOTS : N;
+    const int64_t nb = s->n_blocks;
+    const uint64_t n_rows = (uint64_t)N * TOP_BLOCK_ROWS;
+    const uint64_t n_slot_rows = (uint64_t)slots * TOP_BLOCK_ROWS;
+    int rc;
+    if (s->top_blocks_cap < nb) {
+        if ((rc = top_alloc(s, &s->d_top_bkeys, (uint64_t)nb)) ||
+            (rc = top_alloc(s, &s->d_top_bvalid, (uint64_t)nb)))
+            return rc;
+        s->top_blocks_cap = nb;
+    }
+    if (s->rows_blocks_cap < nb) {
+        if ((rc = top_alloc(s, &s->d_rows_blo, (uint64_t)nb))) return rc;
+        s->rows_blocks_cap = nb;
+    }
+    if (s->top_grid_cap != (int64_t)slots) {
+        s->top_grid_cap = 0;
+        if ((rc = top_alloc(s, &s->d_top_grid, n_slot_rows)) ||
+            (rc = top_alloc(s, &s->d_top_rvalid, n_slot_rows)) ||
+            (rc = top_alloc(s, &s->d_top_chosen, (uint64_t)slots)) ||
+            (rc = top_alloc(s, &s->d_top_winners, (uint64_t)slots)) ||
+            (rc = top_alloc(s, &s->d_top_range, (uint64_t)slots)) ||
+            (rc = top_alloc(s, &s->d_top_recs, (uint64_t)slots)))
+            return rc;
+        s->top_grid_cap = (int64_t)slots;
+    }
+    const uint64_t most = (uint64_t)nb > n_rows ? (uint64_t)nb : n_rows;
+    const uint64_t chunks = (most + TOP_CHUNK - 1) / TOP_CHUNK;
+    if (s->top_cnt_cap < chunks) {
+        if ((rc = top_alloc(s, &s->d_top_cnt, 2 * chunks))) return rc;
+        s->top_cnt_cap = chunks;
+    }
+    if (!s->d_rows_st && (rc = top_alloc(s, &s->d_rows_st, 4))) return rc;
+    TopSelState *st_blocks = &s->d_rows_st[1], *st_rows = &s->d_rows_st[3];
+    const uint64_t limit = s->payload_cap + 4096;
+    HIP_TRY(s, hipEventRecord(s->ev_start, s->stream));
+    HIP_TRY(s, hipMemsetAsync(s->d_top_bvalid, 0, (size_t)nb, s->stream));
+    HIP_TRY(s, hipMemsetAsync(s->d_top_rvalid, 0, (size_t)n_rows, s->stream));
+    int64_t wgs = (nb + 3) / 4;                    // one wave per block
+    int grid = (int)(wgs < 8192 ? wgs : 8192);     // grid-stride beyond
+    hipLaunchKernelGGL(k_rows_bounds, dim3(grid), dim3(256), 0, s->stream,
+                       s->d_payload, s->d_sidecar, limit, s->d_blocks, nb,
+                       min_ts, max_ts, flags, s->rows_desc, preds, n_preds,
+                       s->d_pred_bm, s->d_pred_flags, s->d_top_bkeys,
+                       s->d_rows_blo, s->d_top_bvalid, s->d_err);
+    const int64_t ts_wgs = (nb + WAVE - 1) / WAVE;   // 64 blocks per step
+    hipLaunchKernelGGL(k_rows_bounds_ts,
+                       dim3((unsigned)((int64_t)slots < ts_wgs ? slots : ts_wgs)),
+                       dim3(WAVE), 0, s->stream, s->d_payload, limit,
+                       s->d_blocks, nb, s->rows_desc, s->d_top_bkeys,
+                       s->d_top_bvalid, s->d_top_grid, s->d_err);
+    HIP_TRY(s, hipGetLastError());
+    if ((rc = rows_select(s, s->d_top_bkeys, s->d_rows_blo, nullptr,
+                          s->d_top_bvalid, (uint64_t)nb, N, &s->d_rows_st[0],
+                          st_blocks, s->d_top_chosen)))
+        return rc;
+    hipLaunchKernelGGL(k_top_row_range, dim3((N + 3) / 4), dim3(256), 0,
+                       s->stream, s->d_payload, s->d_blocks, nb, min_ts,
+                       max_ts, flags, st_blocks, s->d_top_chosen,
+                       s->d_top_range, N, s->d_err);
+    hipLaunchKernelGGL(k_rows_row_keys, dim3(N), dim3(WAVE), 0, s->stream,
+                       s->d_payload, s->d_sidecar, limit, s->d_blocks, nb,
+                       s->rows_desc, preds, n_preds, s->d_pred_bm,
+                       s->d_pred_flags, st_blocks, s->d_top_chosen,
+                       s->d_top_range, s->d_top_grid, s->d_top_rvalid,
+                       s->d_err);
+    HIP_TRY(s, hipGetLastError());
+    if ((rc = rows_select(s, s->d_top_grid, s->d_rows_blo, s->d_top_chosen,
+                          s->d_top_rvalid, n_rows, N, &s->d_rows_st[2],
+                          st_rows, s->d_top_winners)))
+        return rc;
+    hipLaunchKernelGGL(k_rows_resolve_keys, dim3((N + 255) / 256), dim3(256),
+                       0, s->stream, s->d_blocks, nb, st_rows,
+                       s->d_top_chosen, s->d_top_winners, s->d_top_grid,
+                       s->d_top_recs, N);
+    hipLaunchKernelGGL(k_top_resolve, dim3(N), dim3(WAVE), 0, s->stream,
+                       s->d_payload, limit, s->d_blocks, nb, st_rows,
+                       s->d_top_grid, s->d_top_recs, s->d_err);
+    hipLaunchKernelGGL(k_rows_resolve_field, dim3(N), dim3(WAVE), 0,
+                       s->stream, s->d_payload, limit, s->d_blocks, nb,
+                       st_rows, s->d_top_grid, s->d_top_recs, s->d_err);
+    HIP_TRY(s, hipGetLastError());
+    HIP_TRY(s, hipEventRecord(s->ev_stop, s->stream));
+    return BYDB_OK;
+}
+
+// a top or row-scan session branches to its own pipeline here, and nowhere
+// else
 static int scan_or_top(bydb_session *s, int64_t min_ts, int64_t max_ts,
                        PredBlock *preds, int n_preds) {
-    return s->top_on ? launch_top(s, min_ts, max_ts, preds, n_preds)
-                     : launch_scan(s, min_ts, max_ts, preds, n_preds);
+    return s->rows_on  ? launch_rows(s, min_ts, max_ts, preds, n_preds)
+           : s->top_on ? launch_top(s, min_ts, max_ts, preds, n_preds)
+                       : launch_scan(s, min_ts, max_ts, preds, n_preds);
 }
 
 // The single point where every consume entry point reaches launch_scan.
@@ -6421,6 +6989,153 @@ extern "C" int bydb_top_rows_merge(const bydb_top_row *const *lists,
     *out_n = take;
     if (take > 0 && !out) return BYDB_ERR_BAD_ARG;
     for (int64_t i = 0; i < take; i++) out[i] = *all[(size_t)i].r;
+    return BYDB_OK;
+}
+
+// ---- Scan -> Limit over raw rows: configure, finalize, shard merge ----
+
+static bool rows_window_ok(int64_t offset, int64_t limit) {
+    return offset >= 0 && limit >= 0 && offset <= BYDB_TOP_ROWS_MAX &&
+           limit <= BYDB_TOP_ROWS_MAX - offset;
+}
+
+// queryResult.Less (query.go:913-943) plus this engine's seq tiebreak
+static bool rows_before(int order, int64_t ts_a, uint64_t sid_a, int64_t ts_b,
+                        uint64_t sid_b, bool *tie) {
+    *tie = false;
+    if (ts_a != ts_b)
+        return order == BYDB_ORDER_TS_DESC ? ts_a > ts_b : ts_a < ts_b;
+    if (sid_a != sid_b) return sid_a < sid_b;
+    *tie = true;
+    return false;
+}
+
+extern "C" int bydb_rows_configure(bydb_session *s, int field_vtype,
+                                   int64_t offset, int64_t limit, int order) {
+    if (!rows_window_ok(offset, limit)) {
+        s->err = "row scan window outside 0..BYDB_TOP_ROWS_MAX";
+        return BYDB_ERR_BAD_ARG;
+    }
+    if (order != BYDB_ORDER_TS_ASC && order != BYDB_ORDER_TS_DESC) {
+        s->err = "row scan order must be BYDB_ORDER_TS_ASC or _DESC";
+        return BYDB_ERR_BAD_ARG;
+    }
+    if (field_vtype != BYDB_VT_INT64 && field_vtype != BYDB_VT_FLOAT64) {
+        s->err = "row scan field_vtype must be int64 or float64";
+        return BYDB_ERR_BAD_ARG;
+    }
+    if (field_vtype == BYDB_VT_FLOAT64 && s->float_exp == BYDB_FLOAT_RAW_EXP) {
+        s->err = "row scan over a raw-float session is not supported";
+        return BYDB_ERR_BAD_ARG;
+    }
+    // as bydb_top_configure: a one-group, no-function aggregate that no
+    // kernel ever touches keeps the consume entry points and bydb_reset happy
+    int rc = bydb_agg_configure(s, field_vtype, 0, 1, BYDB_MODE_ALL);
+    if (rc != BYDB_OK) return rc;
+    s->rows_on = true;
+    s->rows_offset = offset;
+    s->rows_limit = limit;
+    s->rows_desc = order == BYDB_ORDER_TS_DESC ? 1 : 0;
+    return BYDB_OK;
+}
+
+extern "C" int bydb_rows_finalize(bydb_session *s, bydb_top_row *out,
+                                  int64_t cap, int64_t *out_n) {
+    HIP_TRY(s, hipSetDevice(s->device));
+    if (!s->rows_on) { s->err = "not a row-scan session"; return BYDB_ERR_STATE; }
+    if (!out_n) { s->err = "null out_n"; return BYDB_ERR_BAD_ARG; }
+    *out_n = 0;
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    if (!s->consumed || s->rows_limit == 0) {
+        s->consumed = false;
+        return BYDB_OK;
+    }
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, s->ev_start, s->ev_stop) == hipSuccess)
+        s->last_ms = ms;
+    DevErr de;
+    HIP_TRY(s, hipMemcpy(&de, s->d_err, sizeof de, hipMemcpyDeviceToHost));
+    if (de.code != DERR_NONE) {
+        char buf[128];
+        snprintf(buf, sizeof buf, "device decode error %u at block %u%s",
+                 de.code, de.block_lo,
+                 de.code == DERR_TOP_NULL
+                     ? " (row scan selected a row of a null-bearing block)"
+                     : "");
+        s->err = buf;
+        return BYDB_ERR_BAD_DATA;
+    }
+    TopSelState st;
+    HIP_TRY(s, hipMemcpy(&st, &s->d_rows_st[3], sizeof st,
+                         hipMemcpyDeviceToHost));
+    const int64_t sel = (int64_t)st.n_out;
+    if (sel > s->rows_offset + s->rows_limit) {
+        s->err = "row selector overran";
+        return BYDB_ERR;
+    }
+    const int64_t got = sel > s->rows_offset ? sel - s->rows_offset : 0;
+    *out_n = got;
+    if (cap < got || (got > 0 && !out)) {
+        s->err = "rows_finalize: out holds fewer rows than the window";
+        return BYDB_ERR_OOM;   // the epoch stays open: call again
+    }
+    std::vector<TopRec> recs((size_t)sel);
+    if (sel > 0)
+        HIP_TRY(s, hipMemcpy(recs.data(), s->d_top_recs,
+                             sizeof(TopRec) * (size_t)sel,
+                             hipMemcpyDeviceToHost));
+    const int order = s->rows_desc ? BYDB_ORDER_TS_DESC : BYDB_ORDER_TS_ASC;
+    std::sort(recs.begin(), recs.end(),
+              [order](const TopRec &a, const TopRec &b) {
+                  bool tie;
+                  bool lt = rows_before(order, a.ts, a.series_id, b.ts,
+                                        b.series_id, &tie);
+                  return tie ? a.seq < b.seq : lt;
+              });
+    const bool is_f = s->field_vtype == BYDB_VT_FLOAT64;
+    for (int64_t i = 0; i < got; i++) {
+        const TopRec &r = recs[(size_t)(s->rows_offset + i)];
+        bydb_top_row *o = &out[i];
+        o->series_id = r.series_id;
+        o->ts = r.ts;
+        o->version = r.version;
+        o->value_i = r.value;
+        o->value_f = is_f ? restore_f64(r.value, (int16_t)r.exp) : 0.0;
+        o->seq = r.seq;
+    }
+    s->consumed = false;
+    return BYDB_OK;
+}
+
+extern "C" int bydb_rows_merge(const bydb_top_row *const *lists,
+                               const int64_t *lens, int n_lists,
+                               int64_t offset, int64_t limit, int order,
+                               bydb_top_row *out, int64_t *out_n) {
+    if (!out_n || n_lists < 0 || !rows_window_ok(offset, limit) ||
+        (n_lists > 0 && (!lists || !lens)) ||
+        (order != BYDB_ORDER_TS_ASC && order != BYDB_ORDER_TS_DESC))
+        return BYDB_ERR_BAD_ARG;
+    *out_n = 0;
+    struct Ent { const bydb_top_row *r; int list; };
+    std::vector<Ent> all;
+    for (int l = 0; l < n_lists; l++) {
+        if (lens[l] < 0 || (lens[l] > 0 && !lists[l])) return BYDB_ERR_BAD_ARG;
+        for (int64_t i = 0; i < lens[l]; i++) all.push_back({&lists[l][i], l});
+    }
+    std::stable_sort(all.begin(), all.end(), [&](const Ent &a, const Ent &b) {
+        bool tie;
+        bool lt = rows_before(order, a.r->ts, a.r->series_id, b.r->ts,
+                              b.r->series_id, &tie);
+        if (!tie) return lt;
+        if (a.list != b.list) return a.list < b.list;
+        return a.r->seq < b.r->seq;
+    });
+    const int64_t total = (int64_t)all.size();
+    int64_t take = total > offset ? total - offset : 0;
+    if (take > limit) take = limit;
+    *out_n = take;
+    if (take > 0 && !out) return BYDB_ERR_BAD_ARG;
+    for (int64_t i = 0; i < take; i++) out[i] = *all[(size_t)(offset + i)].r;
     return BYDB_OK;
 }
 

@@ -754,6 +754,88 @@ int bydb_top_rows_merge(const bydb_top_row *const *lists, const int64_t *lens,
                         int n_lists, int field_vtype, int64_t n, int asc,
                         bydb_top_row *out, int64_t *out_n);
 
+/* ---- time-ordered rows with offset and limit: Scan -> Limit ----
+ * With neither `agg` nor `top` a measure query's plan is Scan -> Limit
+ * (pkg/query/vectorized/measure/plan/analyzer.go:118-157): "the 100 latest
+ * data points of these series in the last hour where env = prod", or "rows
+ * 200..299 in time order".  In the reference that is two pieces.
+ * queryResult's heap merges the block cursors of all parts
+ * (banyand/measure/query.go:913-943, 962-1026): by timestamp (orderByTS,
+ * ascending by default; SORT_DESC walks the cursors backwards, :286-296),
+ * equal timestamps by seriesID ascending, and equal (series, timestamp)
+ * keeps only the highest version.  BatchLimit then keeps rows
+ * [offset, offset + limit) of that stream (limit.go:81-108).  This is both
+ * on the operator seam of the top-N section: the session selects rows
+ * instead of folding them.
+ *
+ * Order contract, a total order on the selected rows: (ts in the requested
+ * direction, series_id ascending, seq ascending), seq = (item << 13) | row.
+ * ts compares as a signed 64-bit value, series_id as an unsigned one.
+ *  - With bydb_set_row_dedup(s, 1), (series_id, ts) is unique among the
+ *    selected rows, so the order is exactly the reference's:
+ *    queryResult.Less gives the first two components and merge keeps the
+ *    highest version.
+ *  - With row dedup off, every resident duplicate surfaces, in seq order
+ *    after (ts, series_id).  The reference always dedups in its merge; this
+ *    is this engine's rule for the off case.
+ *
+ * One limit, kept from top-N: a consume that selects any row of a
+ * null-bearing field block (BYDB_ENC_PLAIN cells) is a loud device error
+ * (bydb_rows_finalize returns BYDB_ERR_BAD_DATA); a null is never returned
+ * as a value.  A Plain block the clamp or the filter leaves no row of is
+ * not an error.  Raw-float sessions (BYDB_FLOAT_RAW_EXP) consist of such
+ * blocks and are out of scope. */
+enum { BYDB_ORDER_TS_ASC = 0, BYDB_ORDER_TS_DESC = 1 };
+
+/* BuildOperators' plan without GroupByAgg and Top (analyzer.go:118-157):
+ * makes the session a row-scan operator that keeps rows
+ * [offset, offset + limit) of the ordered selection (NewBatchLimit,
+ * limit.go:40-53); a later bydb_agg_configure* or bydb_top_configure
+ * switches it back.  BYDB_ERR_BAD_ARG (session stays usable, configuration
+ * unchanged) when offset < 0, limit < 0, offset + limit >
+ * BYDB_TOP_ROWS_MAX, order is not one of BYDB_ORDER_TS_*, field_vtype is
+ * not int64 / float64, or the session exponent is BYDB_FLOAT_RAW_EXP (also
+ * checked by the consume).  limit == 0 is legal: consume launches nothing,
+ * finalize returns 0 rows; substituting the analyzer's defaultLimit
+ * (analyzer.go:153-157) is the host's job.  field_vtype names the field
+ * whose value each row carries; for float64 the session exponent
+ * (bydb_set_float_exp) is the part's minimum exponent, as for aggregates.
+ *
+ * Every consume entry point (bydb_consume, _multi, _filter, _filter_tree,
+ * with or without bydb_set_row_dedup) then selects under exactly the
+ * aggregate path's rules: clamp, skip verdicts, code-mask and bitmap
+ * walkers, dedup survivors removed before the filter.  One consume per
+ * epoch: a second one before bydb_rows_finalize or bydb_reset is
+ * BYDB_ERR_STATE.  bydb_last_consume_ms reports the event-timed span of all
+ * row-scan kernels. */
+int bydb_rows_configure(bydb_session *s, int field_vtype,
+                        int64_t offset, int64_t limit, int order);
+
+/* BatchLimit.Process over the merged stream (limit.go:81-108): syncs, then
+ * writes rows [offset, offset + limit) of the ordered selection — fewer, or
+ * none, when the selection is shorter — and their count to *out_n, and
+ * closes the epoch.  Every field of bydb_top_row is filled as
+ * bydb_top_finalize fills it: value_i is the row's value (float64: its
+ * decimal mantissa in its own block's exponent), value_f the restore of
+ * that.  BYDB_ERR_OOM when cap is smaller than the count: *out_n holds the
+ * needed count and the epoch stays open.  BYDB_ERR_STATE when the session
+ * is not a row-scan session, BYDB_ERR_BAD_DATA on a device error (sticky
+ * until bydb_reset). */
+int bydb_rows_finalize(bydb_session *s, bydb_top_row *out, int64_t cap,
+                       int64_t *out_n);
+
+/* Pure host, no GPU, no session: the reduce side for time-bucket shards.
+ * Each shard is configured with offset 0 and limit offset + limit; this
+ * merges the per-shard bydb_rows_finalize results by (ts in the requested
+ * direction, series_id ascending) — on a full tie the earlier list first,
+ * then the smaller seq — and then cuts [offset, offset + limit).  out holds
+ * at most `limit` rows and must not alias a list.  BYDB_ERR_BAD_ARG on
+ * null outputs, negative counts, offset + limit > BYDB_TOP_ROWS_MAX or an
+ * unknown order. */
+int bydb_rows_merge(const bydb_top_row *const *lists, const int64_t *lens,
+                    int n_lists, int64_t offset, int64_t limit, int order,
+                    bydb_top_row *out, int64_t *out_n);
+
 /* ---- AggModeReduce over raw map frames, with replica dedup ----
  * Restates the liaison reduce (aggregation_reduce.go:83-138 +
  * ReduceRawFrames, reduce.go:78): rows keyed by the key columns
