@@ -4975,6 +4975,15 @@ extern "C" int bydb_set_stream_policy(bydb_session *s, int policy) {
     return BYDB_OK;
 }
 
+// Grid caps of the per-block kernels (host side only; the kernels go round a
+// grid-stride loop past them).  tests/test_loop_trips_cpu.py reads these two
+// lines: its parts must stay larger than both.
+// k_scan_agg_t, k_top_bounds, k_rows_bounds: 256-thread workgroups, one wave
+// per block
+#define SCAN_MAX_WGS 8192
+// the 64-thread kernels that take one block per workgroup
+#define BLOCK_KERNEL_MAX_WGS 65535
+
 #define HIP_TRY(s, call)                                                      \
     do {                                                                      \
         hipError_t _e = (call);                                               \
@@ -5539,7 +5548,8 @@ static int pack_build(bydb_session *s) {
                               hipMemcpyHostToDevice, s->stream));
     HIP_TRY(s, hipMemsetAsync(s->d_pack_ctr, 0, 2 * sizeof(unsigned long long),
                               s->stream));
-    const int grid = (int)(nb < 65535 ? nb : 65535);
+    const int grid =
+        (int)(nb < BLOCK_KERNEL_MAX_WGS ? nb : BLOCK_KERNEL_MAX_WGS);
     hipLaunchKernelGGL(k_pack_fields, dim3(grid), dim3(WAVE), 0, s->stream,
                        s->d_payload, s->d_blocks, nb, s->d_pack, s->d_pack_ctr);
     HIP_TRY(s, hipGetLastError());
@@ -5622,8 +5632,9 @@ static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
                     s->d_gmap, (uint32_t)((int64_t)i * 256 * s->n_blocks));
                 HIP_TRY(s, hipGetLastError());
                 if (s->n_plain_host > 0) {
-                    int pgrid =
-                        (int)(s->n_blocks < 65535 ? s->n_blocks : 65535);
+                    int pgrid = (int)(s->n_blocks < BLOCK_KERNEL_MAX_WGS
+                                          ? s->n_blocks
+                                          : BLOCK_KERNEL_MAX_WGS);
                     hipLaunchKernelGGL(
                         k_resolve_plain_groups, dim3(pgrid), dim3(WAVE), 0,
                         s->stream, s->d_payload, s->d_sidecar, s->d_blocks,
@@ -5638,7 +5649,7 @@ static int launch_scan(bydb_session *s, int64_t min_ts, int64_t max_ts,
         groups = s->d_groups;
     }
     int64_t wgs = (s->n_blocks + 3) / 4;            // one wave per block
-    int grid = (int)(wgs < 8192 ? wgs : 8192);     // grid-stride beyond
+    int grid = (int)(wgs < SCAN_MAX_WGS ? wgs : SCAN_MAX_WGS);  // stride beyond
     if (grid < 1) grid = 1;
     const bool en_values = (flags & KF_NEED_VALUES) != 0;
     const bool en_preds = n_preds > 0;
@@ -5922,7 +5933,8 @@ static int dedup_build(bydb_session *s) {
                               hipMemcpyHostToDevice, s->stream));
     HIP_TRY(s, hipMemsetAsync(s->d_dd_ctr, 0, 4 * sizeof(unsigned long long),
                               s->stream));
-    const int grid = (int)(n_inv < 65535 ? n_inv : 65535);
+    const int grid =
+        (int)(n_inv < BLOCK_KERNEL_MAX_WGS ? n_inv : BLOCK_KERNEL_MAX_WGS);
     hipLaunchKernelGGL(k_dedup_decode, dim3(grid), dim3(WAVE), 0, s->stream,
                        s->d_payload, s->payload_cap + 4096, s->d_blocks,
                        s->d_dd_infos, n_inv, s->d_dd_arena, s->d_err);
@@ -6060,7 +6072,7 @@ static int launch_top(bydb_session *s, int64_t min_ts, int64_t max_ts,
     HIP_TRY(s, hipMemsetAsync(s->d_top_bvalid, 0, (size_t)nb, s->stream));
     HIP_TRY(s, hipMemsetAsync(s->d_top_rvalid, 0, (size_t)n_rows, s->stream));
     int64_t wgs = (nb + 3) / 4;                    // one wave per block
-    int grid = (int)(wgs < 8192 ? wgs : 8192);     // grid-stride beyond
+    int grid = (int)(wgs < SCAN_MAX_WGS ? wgs : SCAN_MAX_WGS);  // stride beyond
     hipLaunchKernelGGL(k_top_bounds, dim3(grid), dim3(256), 0, s->stream,
                        s->d_payload, s->d_sidecar, s->d_blocks, nb, min_ts,
                        max_ts, flags, s->top_asc, preds, n_preds, s->d_pred_bm,
@@ -6194,7 +6206,7 @@ static int launch_rows(bydb_session *s, int64_t min_ts, int64_t max_ts,
     HIP_TRY(s, hipMemsetAsync(s->d_top_bvalid, 0, (size_t)nb, s->stream));
     HIP_TRY(s, hipMemsetAsync(s->d_top_rvalid, 0, (size_t)n_rows, s->stream));
     int64_t wgs = (nb + 3) / 4;                    // one wave per block
-    int grid = (int)(wgs < 8192 ? wgs : 8192);     // grid-stride beyond
+    int grid = (int)(wgs < SCAN_MAX_WGS ? wgs : SCAN_MAX_WGS);  // stride beyond
     hipLaunchKernelGGL(k_rows_bounds, dim3(grid), dim3(256), 0, s->stream,
                        s->d_payload, s->d_sidecar, limit, s->d_blocks, nb,
                        min_ts, max_ts, flags, s->rows_desc, preds, n_preds,
@@ -6270,7 +6282,9 @@ static int scan_deduped(bydb_session *s, int64_t min_ts, int64_t max_ts,
     }
     int64_t route_wgs = (s->dd_n_full + WAVE - 1) / WAVE;
     int64_t want = s->dd_n_partial > route_wgs ? s->dd_n_partial : route_wgs;
-    int grid = (int)(want < 1 ? 1 : want < 65535 ? want : 65535);
+    int grid = (int)(want < 1 ? 1
+                     : want < BLOCK_KERNEL_MAX_WGS ? want
+                                                   : BLOCK_KERNEL_MAX_WGS);
     hipLaunchKernelGGL(k_dedup_apply, dim3(grid), dim3(WAVE), 0, s->stream,
                        s->d_payload, s->d_sidecar, s->d_blocks, s->n_blocks,
                        s->d_dd_plist, s->dd_n_partial, s->d_dd_flist,
@@ -6502,7 +6516,9 @@ static int consume_conds(bydb_session *s, int64_t min_ts, int64_t max_ts,
     if (s->n_plain_host > 0) {
         HIP_TRY(s, hipMemsetAsync(s->d_plain_ctr, 0, sizeof(uint32_t),
                                   s->stream));
-        int pgrid = (int)(s->n_blocks < 65535 ? s->n_blocks : 65535);
+        int pgrid = (int)(s->n_blocks < BLOCK_KERNEL_MAX_WGS
+                              ? s->n_blocks
+                              : BLOCK_KERNEL_MAX_WGS);
         for (int sl = 0; sl < fs.n_slots; sl++) {
             if (fs.first[sl] == fs.first[sl + 1]) continue;
             hipLaunchKernelGGL(k_resolve_plain_filter, dim3(pgrid), dim3(WAVE),
@@ -6671,7 +6687,9 @@ extern "C" int bydb_consume_filter_tree(bydb_session *s, int64_t min_ts,
     if (n_row_blocks > 0) {
         HIP_TRY(s, hipMemsetAsync(s->d_plain_ctr, 0, sizeof(uint32_t),
                                   s->stream));
-        int pgrid = (int)(s->n_blocks < 65535 ? s->n_blocks : 65535);
+        int pgrid = (int)(s->n_blocks < BLOCK_KERNEL_MAX_WGS
+                              ? s->n_blocks
+                              : BLOCK_KERNEL_MAX_WGS);
         hipLaunchKernelGGL(k_resolve_tree_rows, dim3(pgrid), dim3(WAVE), 0,
                            s->stream, s->d_payload, s->d_sidecar, s->d_blocks,
                            s->n_blocks, fs, ts, s->d_preds, s->d_pred_flags,
