@@ -84,6 +84,8 @@ OP_IN, OP_NOT_IN = 9, 10
 TAG_STRING, TAG_INT = 1, 2
 FILTER_MAX_CONDS = 8
 TOP_ROWS_MAX = 1024
+TAG_FETCH_MAX = TOP_ROWS_MAX   # rows per fetch_tags call
+ERR_OOM = -7
 ORDER_TS_ASC, ORDER_TS_DESC = 0, 1
 
 
@@ -411,6 +413,29 @@ def _load():
                                     C.POINTER(C.c_int64), C.c_int, C.c_int64,
                                     C.c_int64, C.c_int, C.POINTER(TopRow),
                                     C.POINTER(C.c_int64)]
+    lib.bydb_rows_fetch_tags.restype = C.c_int
+    lib.bydb_rows_fetch_tags.argtypes = [C.c_void_p, C.POINTER(C.c_uint64),
+                                         C.c_int64, C.c_int,
+                                         C.POINTER(C.c_uint8), C.c_uint64,
+                                         C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint8),
+                                         C.POINTER(C.c_uint64)]
+    lib.bydb_rows_merge_src.restype = C.c_int
+    lib.bydb_rows_merge_src.argtypes = [C.POINTER(C.POINTER(TopRow)),
+                                        C.POINTER(C.c_int64), C.c_int,
+                                        C.c_int64, C.c_int64, C.c_int,
+                                        C.POINTER(TopRow),
+                                        C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int64)]
+    lib.bydb_top_rows_merge_src.restype = C.c_int
+    lib.bydb_top_rows_merge_src.argtypes = [C.POINTER(C.POINTER(TopRow)),
+                                            C.POINTER(C.c_int64), C.c_int,
+                                            C.c_int, C.c_int64, C.c_int,
+                                            C.POINTER(TopRow),
+                                            C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int64)]
     lib.bydb_reduce_partials2.restype = C.c_int
     lib.bydb_reduce_partials2.argtypes = [C.POINTER(Partial), C.c_int64, C.c_int64,
                                           C.c_int, C.c_int16, C.POINTER(Result)]
@@ -766,6 +791,35 @@ class Session:
         self._ck(_lib.bydb_rows_finalize(self._h, out, cap, C.byref(got)))
         return [out[i] for i in range(got.value)]
 
+    def fetch_tags(self, seqs_or_rows, slot):
+        """Tag values of result rows on one block tag slot (block.go:509-776
+        copyTo, query.go:641 mustDecodeTagValue): a list, in request order,
+        of the stored cell bytes, None for a nil value (b"" is a real
+        value).  Takes the TopRow of top_rows() / scan_rows() or plain seq
+        ints, at most TAG_FETCH_MAX a call.  A gather over the resident
+        part: it belongs to no epoch and changes none."""
+        seqs = [r.seq if isinstance(r, TopRow) else int(r)
+                for r in seqs_or_rows]
+        n = len(seqs)
+        arr = (C.c_uint64 * max(n, 1))(*seqs)
+        offs = (C.c_uint64 * (n + 1))()
+        nil = (C.c_uint8 * max(n, 1))()
+        total = C.c_uint64(0)
+        # a first call without a buffer sizes it
+        rc = _lib.bydb_rows_fetch_tags(self._h, arr, n, slot, None, 0, offs,
+                                       nil, C.byref(total))
+        if rc == ERR_OOM and total.value > 0:
+            data = (C.c_uint8 * total.value)()
+            rc = _lib.bydb_rows_fetch_tags(self._h, arr, n, slot, data,
+                                           total.value, offs, nil,
+                                           C.byref(total))
+        else:
+            data = (C.c_uint8 * 1)()
+        self._ck(rc)
+        raw = bytes(data)
+        return [None if nil[i] else raw[offs[i]:offs[i + 1]]
+                for i in range(n)]
+
     def set_partials_buffer(self, dev_ptr, nbytes):
         self._ck(_lib.bydb_set_partials_buffer(self._h, dev_ptr, nbytes))
 
@@ -890,40 +944,65 @@ def reduce_partials(parts_flat, n_parts_per_group, n_groups, field_vtype,
     return list(out)
 
 
-def top_rows_merge(lists, field_vtype, n, asc=False):
+def _with_src(out, src_l, src_i, got):
+    n = got.value
+    return ([out[i] for i in range(n)], [src_l[i] for i in range(n)],
+            [src_i[i] for i in range(n)])
+
+
+def top_rows_merge(lists, field_vtype, n, asc=False, with_src=False):
     """Host reduce side of a sharded raw-row top-N: a stable N-way merge of
     per-shard top_rows() results (lists of TopRow).  On equal values the
-    earlier list wins, then the smaller seq."""
+    earlier list wins, then the smaller seq.  with_src: return (rows,
+    list_idx, row_idx) with rows[i] == lists[list_idx[i]][row_idx[i]] — seq
+    is shard-local, so this names the session to fetch a row's tags from."""
     arrs = [(TopRow * max(len(l), 1))(*l) for l in lists]
     ptrs = (C.POINTER(TopRow) * max(len(lists), 1))(
         *[C.cast(a, C.POINTER(TopRow)) for a in arrs])
     lens = (C.c_int64 * max(len(lists), 1))(*[len(l) for l in lists])
     total = sum(len(l) for l in lists)
-    out = (TopRow * max(min(total, max(n, 0)), 1))()
+    cap = max(min(total, max(n, 0)), 1)
+    out = (TopRow * cap)()
     got = C.c_int64(0)
-    rc = _lib.bydb_top_rows_merge(ptrs, lens, len(lists), field_vtype, n,
-                                  1 if asc else 0, out, C.byref(got))
+    if with_src:
+        src_l, src_i = (C.c_int32 * cap)(), (C.c_int64 * cap)()
+        rc = _lib.bydb_top_rows_merge_src(ptrs, lens, len(lists), field_vtype,
+                                          n, 1 if asc else 0, out, src_l,
+                                          src_i, C.byref(got))
+    else:
+        rc = _lib.bydb_top_rows_merge(ptrs, lens, len(lists), field_vtype, n,
+                                      1 if asc else 0, out, C.byref(got))
     if rc != 0:
         raise RuntimeError(f"top_rows_merge rc={rc}")
+    if with_src:
+        return _with_src(out, src_l, src_i, got)
     return [out[i] for i in range(got.value)]
 
 
-def rows_merge(lists, offset, limit, desc=False):
+def rows_merge(lists, offset, limit, desc=False, with_src=False):
     """Host reduce side of a sharded row scan: per-shard scan_rows() results
     (each configured with offset 0 and limit offset + limit) merged by
     (timestamp, series_id), the earlier list first on a full tie, then cut
-    to [offset, offset + limit)."""
+    to [offset, offset + limit).  with_src: as for top_rows_merge."""
     arrs = [(TopRow * max(len(l), 1))(*l) for l in lists]
     ptrs = (C.POINTER(TopRow) * max(len(lists), 1))(
         *[C.cast(a, C.POINTER(TopRow)) for a in arrs])
     lens = (C.c_int64 * max(len(lists), 1))(*[len(l) for l in lists])
-    out = (TopRow * max(limit, 1))()
+    cap = max(limit, 1)
+    out = (TopRow * cap)()
     got = C.c_int64(0)
-    rc = _lib.bydb_rows_merge(ptrs, lens, len(lists), offset, limit,
-                              ORDER_TS_DESC if desc else ORDER_TS_ASC, out,
-                              C.byref(got))
+    order = ORDER_TS_DESC if desc else ORDER_TS_ASC
+    if with_src:
+        src_l, src_i = (C.c_int32 * cap)(), (C.c_int64 * cap)()
+        rc = _lib.bydb_rows_merge_src(ptrs, lens, len(lists), offset, limit,
+                                      order, out, src_l, src_i, C.byref(got))
+    else:
+        rc = _lib.bydb_rows_merge(ptrs, lens, len(lists), offset, limit, order,
+                                  out, C.byref(got))
     if rc != 0:
         raise RuntimeError(f"rows_merge rc={rc}")
+    if with_src:
+        return _with_src(out, src_l, src_i, got)
     return [out[i] for i in range(got.value)]
 
 

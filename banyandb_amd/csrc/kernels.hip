@@ -4828,6 +4828,229 @@ __global__ __launch_bounds__(WAVE) void k_rows_resolve_field(
     if (lane == 0) recs[i].value = v;
 }
 
+// ---- tag projection for row results: fetch tag values by seq ----
+// The reference decodes every projected tag column of each emitted row
+// (blockCursor.copyTo / copyAllTo, block.go:509-776, through
+// mustDecodeTagValue, query.go:641).  Here the winners of a top / row scan
+// carry seq = (block << 13) | row, and this gather returns the stored cell
+// bytes of up to BYDB_TAG_FETCH_MAX such rows on one tag slot: locate
+// (one wave per row) -> offsets (one workgroup) -> copy (one wave per row).
+// It reads the resident part only and writes none of the epoch's state.
+//
+// Bounds rule: every range is compared against its stream's end,
+// [tag_off, tag_off + tag_len), before the load that would read it; a range
+// that leaves the stream is TF_BAD_STREAM, never a read.
+#define TF_VALUE 0
+#define TF_NIL 1
+#define TF_BAD_SEQ 2
+#define TF_BAD_STREAM 3
+#define TF_NONE 0xFFFFFFFFu
+
+struct TagFetchRec {
+    uint64_t src;      // arena offset of the value, TAG_SIDECAR_BIT as in descs
+    uint32_t len;
+    uint8_t status;    // TF_*
+    uint8_t _p[3];
+};
+
+struct TagFetchResult {
+    uint64_t total;         // bytes of all values
+    uint32_t bad_seq;       // first request index with TF_BAD_SEQ, or TF_NONE
+    uint32_t bad_stream;    // first request index with TF_BAD_STREAM
+};
+
+// rd_bits_be for a stream that ends at byte offset `end` of p: a byte at or
+// past the end is not loaded and reads as 0 (rd_bits_be always gathers 8)
+__device__ __forceinline__ uint64_t rd_bits_be_in(const uint8_t *p,
+                                                  uint64_t bitpos, uint32_t n,
+                                                  uint64_t end) {
+    uint64_t byte = bitpos >> 3;
+    uint32_t sh = (uint32_t)(bitpos & 7);
+    uint64_t acc = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        uint64_t at = byte + (uint64_t)i;
+        acc = (acc << 8) | (at < end ? p[at] : 0);
+    }
+    return (acc >> (64 - sh - n)) & ((1ull << n) - 1);
+}
+
+// The dictionary code of `row`: the bit-packed RLE (code, count) pairs 64
+// runs per step, one pair per lane; a wave scan of the counts plus the total
+// carried over from the steps before finds the first run whose running total
+// exceeds `row`.  -1 when the runs end before the row.  The caller has
+// checked that the entries lie inside the stream and that 1 <= width <= 32.
+__device__ __forceinline__ int64_t tag_fetch_code(const DictStream &ds,
+                                                  uint64_t end, uint32_t row,
+                                                  int lane) {
+    const uint32_t nruns = ds.nentries >> 1;
+    uint64_t carried = 0;
+    for (uint32_t r0 = 0; r0 < nruns; r0 += WAVE) {
+        const uint32_t r = r0 + (uint32_t)lane;
+        uint64_t code = 0, cnt = 0;
+        if (r < nruns) {
+            uint64_t bit = ds.bit0 + (uint64_t)(2 * r) * ds.width;
+            code = rd_bits_be_in(ds.base, bit, ds.width, end);
+            cnt = rd_bits_be_in(ds.base, bit + ds.width, ds.width, end);
+        }
+        uint64_t incl = carried + wave_incl_scan(cnt, lane);
+        uint64_t hit = __ballot(r < nruns && incl > (uint64_t)row);
+        if (hit)
+            return (int64_t)__shfl((unsigned long long)code,
+                                   (int)__builtin_ctzll(hit));
+        carried = readlane64(incl, WAVE - 1);
+    }
+    return -1;
+}
+
+__global__ __launch_bounds__(WAVE) void k_tag_fetch_locate(
+    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
+    const bydb_block_desc *__restrict__ blocks, int64_t n_blocks,
+    const uint64_t *__restrict__ seqs, int64_t n, int slot,
+    TagFetchRec *__restrict__ recs) {
+    const int lane = threadIdx.x;
+    const int64_t i = blockIdx.x;
+    if (i >= n) return;
+    const uint64_t seq = seqs[i];
+    const uint64_t bi = seq >> 13;
+    const uint32_t row = (uint32_t)(seq & 8191);
+    TagFetchRec rec;
+    rec.src = 0; rec.len = 0; rec.status = TF_NIL;
+    rec._p[0] = rec._p[1] = rec._p[2] = 0;
+    // every exit below is wave-uniform: seq, the descriptor and the stream
+    // header are the same for all lanes
+    if (bi >= (uint64_t)n_blocks || row >= blocks[bi].count) {
+        rec.status = TF_BAD_SEQ;
+        if (lane == 0) recs[i] = rec;
+        return;
+    }
+    const bydb_block_desc *bd = &blocks[bi];
+    DictStream ds;
+    const int kind = tag_open(payload, sidecar, bd, slot, &ds);
+    if (kind == TS_NIL) {
+        if (lane == 0) recs[i] = rec;
+        return;
+    }
+    rec.status = TF_BAD_STREAM;
+    uint64_t toff, tlen;
+    tag_slot(bd, slot, &toff, &tlen);
+    const uint64_t side = toff & TAG_SIDECAR_BIT;
+    const uint64_t end = (toff & ~TAG_SIDECAR_BIT) + tlen;  // offset in base
+    if (kind == TS_DICT) {
+        // sections in order, all inside the stream: lengths, values, the
+        // 5-byte entry header, the packed entries
+        const uint64_t lens_off = (uint64_t)(ds.lens - ds.base);
+        const uint64_t vals_off = (uint64_t)(ds.vals - ds.base);
+        const uint64_t ent_off = ds.bit0 >> 3;
+        const uint64_t ent_bits = (uint64_t)ds.nentries * ds.width;
+        bool ok = ds.count <= tlen && vals_off <= end && ent_off <= end &&
+                  lens_off + ds.count * ds.wbytes <= vals_off &&
+                  ds.width >= 1 && ds.width <= 32 &&
+                  ent_bits <= (end - ent_off) * 8;
+        int64_t code = ok ? tag_fetch_code(ds, end, row, lane) : -1;
+        if (code >= 0 && (uint64_t)code < ds.count) {
+            // the value's offset: the stored lengths of the values below
+            // the code, lanes striding the list, one wave reduction
+            uint64_t part = 0;
+            for (uint64_t v = (uint64_t)lane; v < (uint64_t)code; v += WAVE) {
+                uint64_t alen = be_len(ds.lens, v, ds.wbytes);
+                part += alen ? alen - 1 : 0;
+            }
+            const uint64_t voff = wave_reduce_add(part);
+            const uint64_t alen = be_len(ds.lens, (uint64_t)code, ds.wbytes);
+            const uint64_t avail = ent_off - 5 - vals_off;   // values section
+            if (alen == 0) {
+                rec.status = TF_NIL;
+            } else if (ent_off >= vals_off + 5 && voff <= avail &&
+                       alen - 1 <= avail - voff) {
+                rec.status = TF_VALUE;
+                rec.len = (uint32_t)(alen - 1);
+                rec.src = (vals_off + voff) | side;
+            }
+        }
+    } else if (kind == TS_PLAIN && side && tlen >= 6) {
+        // a plain column reaches the device only host-normalised
+        PlainStream ps;
+        if (plain_open(payload, sidecar, bd, slot, &ps)) {
+            const uint64_t hdr = (toff & ~TAG_SIDECAR_BIT) + 6;
+            const uint64_t vals_off = hdr + ps.n * ps.wbytes;   // n <= 8192
+            if (vals_off <= end) {
+                uint64_t carry = 0;
+                PlainRow r = {};
+                for (uint64_t base = 0; base <= (uint64_t)row; base += WAVE)
+                    r = plain_chunk(ps, base, lane, &carry);
+                const uint64_t lp1 =
+                    __shfl((unsigned long long)r.lp1, (int)(row & 63));
+                const uint64_t off =
+                    __shfl((unsigned long long)r.off, (int)(row & 63));
+                const uint64_t avail = end - vals_off;
+                if (lp1 == 0) {
+                    rec.status = TF_NIL;
+                } else if (off <= avail && lp1 - 1 <= avail - off) {
+                    rec.status = TF_VALUE;
+                    rec.len = (uint32_t)(lp1 - 1);
+                    rec.src = (vals_off + off) | side;
+                }
+            }
+        }
+    }
+    if (lane == 0) recs[i] = rec;
+}
+
+// One workgroup: offs[0..n] is the exclusive scan of the n value lengths,
+// nil[i] the nil flag; the first bad index of each kind goes to *res, so the
+// host reads one struct.
+__global__ __launch_bounds__(BYDB_TAG_FETCH_MAX) void k_tag_fetch_offsets(
+    const TagFetchRec *__restrict__ recs, int64_t n,
+    uint64_t *__restrict__ offs, uint8_t *__restrict__ nil,
+    TagFetchResult *__restrict__ res) {
+    __shared__ uint64_t wave_tot[BYDB_TAG_FETCH_MAX / WAVE];
+    __shared__ uint32_t bad[2];
+    const int t = threadIdx.x;
+    const int lane = t & (WAVE - 1);
+    const int w = t / WAVE;
+    if (t < 2) bad[t] = TF_NONE;
+    __syncthreads();
+    uint64_t len = 0;
+    if (t < n) {
+        const TagFetchRec r = recs[t];
+        if (r.status == TF_VALUE) len = r.len;
+        nil[t] = r.status == TF_VALUE ? 0 : 1;
+        if (r.status == TF_BAD_SEQ) atomicMin(&bad[0], (uint32_t)t);
+        if (r.status == TF_BAD_STREAM) atomicMin(&bad[1], (uint32_t)t);
+    }
+    const uint64_t incl = wave_incl_scan(len, lane);
+    if (lane == WAVE - 1) wave_tot[w] = incl;
+    __syncthreads();
+    uint64_t before = 0, total = 0;
+    for (int k = 0; k < BYDB_TAG_FETCH_MAX / WAVE; k++) {
+        if (k < w) before += wave_tot[k];
+        total += wave_tot[k];
+    }
+    if (t < n) offs[t] = before + incl - len;
+    if (t == 0) {
+        offs[n] = total;
+        res->total = total;
+        res->bad_seq = bad[0];
+        res->bad_stream = bad[1];
+    }
+}
+
+// one wave per row: len bytes from the value to out + offs[i], 64 a step
+__global__ __launch_bounds__(WAVE) void k_tag_fetch_copy(
+    const uint8_t *__restrict__ payload, const uint8_t *__restrict__ sidecar,
+    const TagFetchRec *__restrict__ recs, const uint64_t *__restrict__ offs,
+    int64_t n, uint8_t *__restrict__ out) {
+    const int64_t i = blockIdx.x;
+    if (i >= n) return;
+    const TagFetchRec r = recs[i];
+    if (r.status != TF_VALUE) return;
+    const uint8_t *src = ((r.src & TAG_SIDECAR_BIT) ? sidecar : payload) +
+                         (r.src & ~TAG_SIDECAR_BIT);
+    uint8_t *dst = out + offs[i];
+    for (uint32_t k = threadIdx.x; k < r.len; k += WAVE) dst[k] = src[k];
+}
+
 // ===================== host session =====================
 
 struct bydb_session {
@@ -4949,6 +5172,12 @@ struct bydb_session {
     uint64_t *d_rows_blo = nullptr;     // [n_blocks] ~series_id
     int64_t rows_blocks_cap = 0;
     TopSelState *d_rows_st = nullptr;   // [4]: blocks hi, lo; rows hi, lo
+    // Tag projection (bydb_rows_fetch_tags): the request / record / offsets
+    // scratch of one call, a fixed size (TfLayout), and the output arena,
+    // which grows on demand.  Nothing here grows with the part.
+    uint8_t *d_tf = nullptr;
+    uint8_t *d_tf_out = nullptr;
+    uint64_t tf_out_cap = 0;
 };
 
 // What a read-once pass has to exceed before its loads bypass the caches:
@@ -5088,6 +5317,8 @@ extern "C" void bydb_session_destroy(bydb_session *s) {
     dedup_free(s);
     pack_free(s);
     top_free(s);
+    if (s->d_tf) (void)hipFree(s->d_tf);
+    if (s->d_tf_out) (void)hipFree(s->d_tf_out);
     if (s->d_pack_ctr) (void)hipFree(s->d_pack_ctr);
     if (s->ev_start) (void)hipEventDestroy(s->ev_start);
     if (s->ev_stop) (void)hipEventDestroy(s->ev_stop);
@@ -6974,10 +7205,11 @@ extern "C" int bydb_top_finalize(bydb_session *s, bydb_top_row *out,
     return BYDB_OK;
 }
 
-extern "C" int bydb_top_rows_merge(const bydb_top_row *const *lists,
-                                   const int64_t *lens, int n_lists,
-                                   int field_vtype, int64_t n, int asc,
-                                   bydb_top_row *out, int64_t *out_n) {
+extern "C" int bydb_top_rows_merge_src(const bydb_top_row *const *lists,
+                                       const int64_t *lens, int n_lists,
+                                       int field_vtype, int64_t n, int asc,
+                                       bydb_top_row *out, int32_t *out_list,
+                                       int64_t *out_index, int64_t *out_n) {
     if (!out_n || n_lists < 0 || n < 0 || (n_lists > 0 && (!lists || !lens)) ||
         (field_vtype != BYDB_VT_INT64 && field_vtype != BYDB_VT_FLOAT64))
         return BYDB_ERR_BAD_ARG;
@@ -7006,8 +7238,22 @@ extern "C" int bydb_top_rows_merge(const bydb_top_row *const *lists,
     const int64_t take = (int64_t)all.size() < n ? (int64_t)all.size() : n;
     *out_n = take;
     if (take > 0 && !out) return BYDB_ERR_BAD_ARG;
-    for (int64_t i = 0; i < take; i++) out[i] = *all[(size_t)i].r;
+    for (int64_t i = 0; i < take; i++) {
+        const Ent &e = all[(size_t)i];
+        out[i] = *e.r;
+        // where the row came from: the shard to ask for its tags
+        if (out_list) out_list[i] = e.list;
+        if (out_index) out_index[i] = (int64_t)(e.r - lists[e.list]);
+    }
     return BYDB_OK;
+}
+
+extern "C" int bydb_top_rows_merge(const bydb_top_row *const *lists,
+                                   const int64_t *lens, int n_lists,
+                                   int field_vtype, int64_t n, int asc,
+                                   bydb_top_row *out, int64_t *out_n) {
+    return bydb_top_rows_merge_src(lists, lens, n_lists, field_vtype, n, asc,
+                                   out, nullptr, nullptr, out_n);
 }
 
 // ---- Scan -> Limit over raw rows: configure, finalize, shard merge ----
@@ -7125,10 +7371,11 @@ extern "C" int bydb_rows_finalize(bydb_session *s, bydb_top_row *out,
     return BYDB_OK;
 }
 
-extern "C" int bydb_rows_merge(const bydb_top_row *const *lists,
-                               const int64_t *lens, int n_lists,
-                               int64_t offset, int64_t limit, int order,
-                               bydb_top_row *out, int64_t *out_n) {
+extern "C" int bydb_rows_merge_src(const bydb_top_row *const *lists,
+                                   const int64_t *lens, int n_lists,
+                                   int64_t offset, int64_t limit, int order,
+                                   bydb_top_row *out, int32_t *out_list,
+                                   int64_t *out_index, int64_t *out_n) {
     if (!out_n || n_lists < 0 || !rows_window_ok(offset, limit) ||
         (n_lists > 0 && (!lists || !lens)) ||
         (order != BYDB_ORDER_TS_ASC && order != BYDB_ORDER_TS_DESC))
@@ -7153,7 +7400,145 @@ extern "C" int bydb_rows_merge(const bydb_top_row *const *lists,
     if (take > limit) take = limit;
     *out_n = take;
     if (take > 0 && !out) return BYDB_ERR_BAD_ARG;
-    for (int64_t i = 0; i < take; i++) out[i] = *all[(size_t)(offset + i)].r;
+    for (int64_t i = 0; i < take; i++) {
+        const Ent &e = all[(size_t)(offset + i)];
+        out[i] = *e.r;
+        if (out_list) out_list[i] = e.list;
+        if (out_index) out_index[i] = (int64_t)(e.r - lists[e.list]);
+    }
+    return BYDB_OK;
+}
+
+extern "C" int bydb_rows_merge(const bydb_top_row *const *lists,
+                               const int64_t *lens, int n_lists,
+                               int64_t offset, int64_t limit, int order,
+                               bydb_top_row *out, int64_t *out_n) {
+    return bydb_rows_merge_src(lists, lens, n_lists, offset, limit, order, out,
+                               nullptr, nullptr, out_n);
+}
+
+// ---- tag projection for row results ----
+
+// d_tf: what the host uploads, what the kernels keep, and — contiguous, one
+// download — what the host reads back
+struct TfLayout {
+    uint64_t seqs[BYDB_TAG_FETCH_MAX];
+    TagFetchRec recs[BYDB_TAG_FETCH_MAX];
+    struct Back {
+        TagFetchResult res;
+        uint64_t offs[BYDB_TAG_FETCH_MAX + 1];
+        uint8_t nil[BYDB_TAG_FETCH_MAX];
+    } back;
+};
+
+extern "C" int bydb_rows_fetch_tags(bydb_session *s, const uint64_t *seqs,
+                                    int64_t n, int slot, uint8_t *data,
+                                    uint64_t data_cap, uint64_t *offs,
+                                    uint8_t *nil, uint64_t *data_len) {
+    if (n < 0 || n > BYDB_TAG_FETCH_MAX) {
+        s->err = "fetch_tags: n outside 0..BYDB_TAG_FETCH_MAX";
+        return BYDB_ERR_BAD_ARG;
+    }
+    if (slot < 0 || slot > 2) {
+        s->err = "fetch_tags: slot outside 0..2";
+        return BYDB_ERR_BAD_ARG;
+    }
+    if (n == 0) {
+        if (offs) offs[0] = 0;
+        if (data_len) *data_len = 0;
+        return BYDB_OK;
+    }
+    if (!seqs || !offs || !nil || !data_len) {
+        s->err = "fetch_tags: null seqs / offs / nil / data_len";
+        return BYDB_ERR_BAD_ARG;
+    }
+    if (s->n_blocks == 0) {
+        s->err = "fetch_tags: no part is resident";
+        return BYDB_ERR_STATE;
+    }
+    HIP_TRY(s, hipSetDevice(s->device));
+    if (!s->d_tf) {
+        if (hipMalloc(&s->d_tf, sizeof(TfLayout)) != hipSuccess) {
+            (void)hipGetLastError();
+            s->d_tf = nullptr;
+            s->err = "fetch_tags: request scratch allocation failed (" +
+                     std::to_string(sizeof(TfLayout)) + " bytes)";
+            return BYDB_ERR_OOM;
+        }
+    }
+    TfLayout *tf = (TfLayout *)s->d_tf;
+    HIP_TRY(s, hipMemcpyAsync(tf->seqs, seqs, sizeof(uint64_t) * (size_t)n,
+                              hipMemcpyHostToDevice, s->stream));
+    hipLaunchKernelGGL(k_tag_fetch_locate, dim3((unsigned)n), dim3(WAVE), 0,
+                       s->stream, s->d_payload, s->d_sidecar, s->d_blocks,
+                       s->n_blocks, tf->seqs, n, slot, tf->recs);
+    hipLaunchKernelGGL(k_tag_fetch_offsets, dim3(1), dim3(BYDB_TAG_FETCH_MAX),
+                       0, s->stream, tf->recs, n, tf->back.offs, tf->back.nil,
+                       &tf->back.res);
+    HIP_TRY(s, hipGetLastError());
+    // the call's first host wait; it is synchronous by contract
+    static_assert(offsetof(TfLayout::Back, nil) ==
+                      sizeof(TagFetchResult) +
+                          sizeof(uint64_t) * (BYDB_TAG_FETCH_MAX + 1),
+                  "TfLayout::Back is read back as one range");
+    TfLayout::Back back;
+    HIP_TRY(s, hipMemcpyAsync(&back, &tf->back,
+                              offsetof(TfLayout::Back, nil) + (size_t)n,
+                              hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    if (back.res.bad_seq != TF_NONE) {
+        const uint32_t i = back.res.bad_seq;
+        char buf[160];
+        snprintf(buf, sizeof buf,
+                 "fetch_tags: seqs[%u] names block %llu row %u outside the "
+                 "resident part (%lld blocks)",
+                 i, (unsigned long long)(seqs[i] >> 13),
+                 (unsigned)(seqs[i] & 8191), (long long)s->n_blocks);
+        s->err = buf;
+        return BYDB_ERR_BAD_ARG;
+    }
+    if (back.res.bad_stream != TF_NONE) {
+        const uint32_t i = back.res.bad_stream;
+        char buf[160];
+        snprintf(buf, sizeof buf,
+                 "fetch_tags: tag stream of block %llu on slot %d cannot be "
+                 "parsed (seqs[%u])",
+                 (unsigned long long)(seqs[i] >> 13), slot, i);
+        s->err = buf;
+        return BYDB_ERR_BAD_DATA;
+    }
+    const uint64_t total = back.res.total;
+    *data_len = total;
+    memcpy(offs, back.offs, sizeof(uint64_t) * (size_t)(n + 1));
+    memcpy(nil, back.nil, (size_t)n);
+    if (data_cap < total || (total > 0 && !data)) {
+        s->err = "fetch_tags: data holds fewer bytes than the values (" +
+                 std::to_string(total) + ")";
+        return BYDB_ERR_OOM;
+    }
+    if (total == 0) return BYDB_OK;
+    if (s->tf_out_cap < total) {
+        if (s->d_tf_out) (void)hipFree(s->d_tf_out);
+        s->d_tf_out = nullptr;
+        s->tf_out_cap = 0;
+        uint64_t ncap = 64 << 10;
+        while (ncap < total) ncap *= 2;
+        if (hipMalloc(&s->d_tf_out, ncap) != hipSuccess) {
+            (void)hipGetLastError();
+            s->d_tf_out = nullptr;
+            s->err = "fetch_tags: output arena allocation failed (" +
+                     std::to_string(ncap) + " bytes)";
+            return BYDB_ERR_OOM;
+        }
+        s->tf_out_cap = ncap;
+    }
+    hipLaunchKernelGGL(k_tag_fetch_copy, dim3((unsigned)n), dim3(WAVE), 0,
+                       s->stream, s->d_payload, s->d_sidecar, tf->recs,
+                       tf->back.offs, n, s->d_tf_out);
+    HIP_TRY(s, hipGetLastError());
+    HIP_TRY(s, hipMemcpyAsync(data, s->d_tf_out, total, hipMemcpyDeviceToHost,
+                              s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
     return BYDB_OK;
 }
 

@@ -836,6 +836,76 @@ int bydb_rows_merge(const bydb_top_row *const *lists, const int64_t *lens,
                     int n_lists, int64_t offset, int64_t limit, int order,
                     bydb_top_row *out, int64_t *out_n);
 
+/* ---- tag projection for raw-row results: tag values by seq ----
+ * A measure query without `agg` returns data points with their projected
+ * tags: blockCursor.copyTo / copyAllTo (banyand/measure/block.go:509-776)
+ * decode every projected tag column of each emitted row through
+ * mustDecodeTagValue (query.go:641), and the raw-row egress frame carries
+ * them as TagValue columns (bydb_frame_add_tagvalue_*).  This is that seam
+ * for the rows bydb_top_finalize / bydb_rows_finalize return: a gather over
+ * the encoded tag streams already resident on the device, so the host never
+ * decodes a winning block's whole tag column.
+ *
+ * Contract.  For i in [0, n) the tag value on block tag slot `slot` (0-2)
+ * of row (seqs[i] & 8191) of block (seqs[i] >> 13) is
+ * data[offs[i] .. offs[i+1]): values lie back to back in request order,
+ * offs[0] == 0, and *data_len receives the total byte count.  nil[i] == 1
+ * marks a nil value, whose length is 0: a nil dictionary entry, a nil plain
+ * row (stored length 0), or a block with no column on the slot.  The empty
+ * string is a real value: nil[i] == 0 with length 0 — the distinction the
+ * filter section above draws.  The bytes are the stored cell bytes; for int
+ * tags the 8-byte sign-flip cell (convert.Int64ToBytes).  Mapping cells to
+ * typed TagValues is the host's job, as mustDecodeTagValue does it.
+ * Duplicated and unsorted seqs are legal.
+ *
+ * It is a gather over the resident part, not part of an epoch: legal
+ * whenever a part is resident, in any session mode, with an epoch open or
+ * closed.  It leaves the consumed state, the sticky device error,
+ * bydb_last_consume_ms and every top / rows / aggregate buffer untouched.
+ * It runs on the session stream and returns after it has synchronised:
+ * unlike the consume entry points the call is synchronous.
+ *
+ * Errors; none is sticky, the session stays usable after each:
+ *  - BYDB_ERR_BAD_ARG: n < 0 or n > BYDB_TAG_FETCH_MAX; slot outside 0..2; a
+ *    null seqs / offs / nil / data_len with n > 0; a seq whose block index
+ *    is >= the resident block count or whose row is >= that block's count
+ *    (the message names the first offending index).
+ *  - BYDB_ERR_STATE: no part is resident.
+ *  - BYDB_ERR_OOM: data_cap < *data_len, or data is null with a non-zero
+ *    total.  *data_len, offs and nil are valid and data is untouched, so a
+ *    first call with data_cap == 0 sizes the buffer.  Also when the
+ *    session's output arena cannot be allocated (the message names the
+ *    size).
+ *  - BYDB_ERR_BAD_DATA: a tag stream that cannot be parsed — an unknown
+ *    encoding byte, a plain column that was not host-normalised or whose
+ *    row count disagrees with the block's, a dictionary whose sections,
+ *    entries or value would leave the stream, whose runs end before the
+ *    row, or whose code is >= its value count.  The message names the
+ *    block.  Nothing is read outside the stream to find this out.
+ *  - n == 0: BYDB_OK; offs[0] = 0 is written if offs is non-null. */
+#define BYDB_TAG_FETCH_MAX BYDB_TOP_ROWS_MAX   /* rows per call */
+
+int bydb_rows_fetch_tags(bydb_session *s, const uint64_t *seqs, int64_t n,
+                         int slot,
+                         uint8_t *data, uint64_t data_cap,
+                         uint64_t *offs /* n + 1 */, uint8_t *nil /* n */,
+                         uint64_t *data_len);
+
+/* Pure host, no GPU, no session: bydb_rows_merge and bydb_top_rows_merge
+ * with the origin of every merged row.  seq is shard-local, so a host that
+ * merges shards needs to know which shard's session to ask for a merged
+ * row's tags: out[i] == lists[out_list[i]][out_index[i]].  Order and error
+ * rules are exactly those of the two functions above, which are these with
+ * null origin outputs; out_list / out_index may each be null. */
+int bydb_rows_merge_src(const bydb_top_row *const *lists, const int64_t *lens,
+                        int n_lists, int64_t offset, int64_t limit, int order,
+                        bydb_top_row *out, int32_t *out_list, int64_t *out_index,
+                        int64_t *out_n);
+int bydb_top_rows_merge_src(const bydb_top_row *const *lists, const int64_t *lens,
+                            int n_lists, int field_vtype, int64_t n, int asc,
+                            bydb_top_row *out, int32_t *out_list,
+                            int64_t *out_index, int64_t *out_n);
+
 /* ---- AggModeReduce over raw map frames, with replica dedup ----
  * Restates the liaison reduce (aggregation_reduce.go:83-138 +
  * ReduceRawFrames, reduce.go:78): rows keyed by the key columns
